@@ -10,7 +10,11 @@ One "step" = one pass of that whole path over one session already resident in HB
 1 unit = one keypoint at one frame.  Inputs are synthetic (seeded, generated on device).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c3adam|c2|c5|c4|c4w|c4adam|pupil|ekf]
-                  [--scaling weak|strong] [--gather-outputs]
+                  [--scaling weak|strong] [--gather-outputs] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times exactly K steps in one region, and prints the line.  `--full` adds
+everything else described below: back-to-back regions (5 by default), the untimed per-stage kernel pass, the
+CPU baselines with their parity blocks, the host-boundary figure and the `extras` legs.  `--dump-outputs DIR`
+writes what the last timed step returned as DIR/<name>.npy (see dump_outputs).
 N > 1 is launched by torch.distributed.run, one rank per GPU over RCCL.  Default ("weak"): every
 rank smooths its own independent session of the workload's shape (sessions shard with no data-path
 collective; `--workload c5` is BASELINE configs[4]: 128 sessions x 32 keypoints stacked along K per
@@ -78,9 +82,10 @@ def parse():
                         "(configs[2] at K / N keypoints per GPU)")
     p.add_argument('--gather-outputs', action='store_true',
                    help='strong scaling: also time a second loop that all-gathers ms / Vs to every rank')
-    p.add_argument('--regions', type=int, default=5,
-                   help='how many back-to-back timed regions of --steps steps each; ms_per_step / value are the '
-                        'MEDIAN region (max over ranks per region), min / max are reported beside it')
+    p.add_argument('--regions', type=int, default=None,
+                   help='how many back-to-back timed regions of --steps steps each (default 1, with --full 5); '
+                        'ms_per_step / value are the MEDIAN region (max over ranks per region), min / max are '
+                        'reported beside it')
     p.add_argument('--cpu-max-keypoints', type=int, default=0,
                    help='cap on the keypoints of the CPU baseline / parity sample (0: only --cpu-seconds bounds it)')
     p.add_argument('--lean', action='store_true',
@@ -90,7 +95,52 @@ def parse():
                         'single-GPU run reports under `extras`')
     p.add_argument('--master-port', type=int, default=0,
                    help='self-launch (N > 1 without an outer torchrun): rendezvous port, 0 = pick a free one')
-    return p.parse_args()
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last of them returned as DIR/<name>.npy')
+    p.add_argument('--full', action='store_true',
+                   help='also measure and check everything beside the headline figure: CPU baselines and parity, '
+                        'per-stage kernel times, host-boundary rate, the extras legs, 5 timed regions by default')
+    a = p.parse_args()
+    if a.regions is None:
+        a.regions = 5 if a.full else 1
+    if not a.full:
+        # a plain run does only what its headline figure needs: no CPU port, no NumPy / host-boundary figures, no legs
+        a.no_cpu_baseline = a.no_extras = a.lean = True
+    return a
+
+
+DUMP_MAX_BYTES = 60 << 20      # --dump-outputs: 64 MB in all at most, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, T, suffix=''):
+    """--dump-outputs: one DIR/<name><suffix>.npy per entry of `arrays` (name -> (array, frame axis or None)), float32
+    or float64 as computed (other dtypes as float64).  When everything would exceed DUMP_MAX_BYTES, each array with a
+    frame axis keeps the same fixed, seeded sample of its T frames (the first and the last among them), so two builds
+    given the same arguments write files that compare element for element."""
+    import torch
+
+    def nbytes(a):
+        return a.numel() * a.element_size() if torch.is_tensor(a) else np.asarray(a).nbytes
+
+    fixed = sum(nbytes(a) for a, ax in arrays.values() if ax is None)
+    per_frame = sum(nbytes(a) for a, ax in arrays.values() if ax is not None) / T
+    frames = None
+    if fixed + per_frame * T > DUMP_MAX_BYTES:
+        n = int((DUMP_MAX_BYTES - fixed) // per_frame)
+        frames = np.union1d(np.random.default_rng(0).choice(np.arange(1, T - 1), n - 2, replace=False), [0, T - 1])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (a, ax) in arrays.items():
+        if torch.is_tensor(a):
+            if frames is not None and ax is not None:
+                a = a.index_select(ax, torch.as_tensor(frames, device=a.device))
+            a = a.detach().cpu().numpy()
+        else:
+            a = np.asarray(a)
+            if frames is not None and ax is not None:
+                a = np.take(a, frames, axis=ax)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + suffix + '.npy'), np.ascontiguousarray(a))
 
 
 def self_launch(args):
@@ -302,6 +352,7 @@ def bench_dense(args, T, K, dev, rank, world, lib, grad=False):
     s = torch.full((K,), 10.0, dtype=torch.float64, device=dev)
     ms = torch.empty((T, K, D), dtype=torch.float32, device=dev)
     Vs = torch.empty((T, K, D, D), dtype=torch.float32, device=dev)
+    last = {'ms': (ms, 0), 'Vs': (Vs, 0)}
 
     def step():
         hip_ops.smooth(y, var, m0, S0, eye, C, Q, s, out=(ms, Vs))
@@ -309,9 +360,12 @@ def bench_dense(args, T, K, dev, rank, world, lib, grad=False):
     if grad:
         rconst = hip_ops.const_r(var)
         s_col = s[:, None].contiguous()
+        last = {}
 
         def step():                                   # noqa: F811  (Q above is positive definite)
-            hip_ops.nll(y, rconst, m0, S0, eye, C, Q, s_col, per_keypoint=True, want_grad=True, flags=_lib.FLAG_Q_PD)
+            nll, g = hip_ops.nll(y, rconst, m0, S0, eye, C, Q, s_col, per_keypoint=True, want_grad=True,
+                                 flags=_lib.FLAG_Q_PD)
+            last.update(nll=(nll, None), grad=(g, None))
 
     for _ in range(args.warmup):
         step()
@@ -324,13 +378,17 @@ def bench_dense(args, T, K, dev, rank, world, lib, grad=False):
         torch.cuda.synchronize()
         region_dt.append(time.perf_counter() - t0)
     dt = float(np.median(region_dt))
-    lib.eks_profile_drain(None, 0, None, 0)
-    lib.eks_profile_enable(1)
-    for _ in range(5):
-        step()
-    torch.cuda.synchronize()
-    lib.eks_profile_enable(0)
-    prof = {k: float(np.mean(v)) for k, v in drain_profile(lib).items()}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, T)
+    prof = {}
+    if args.full:
+        lib.eks_profile_drain(None, 0, None, 0)
+        lib.eks_profile_enable(1)
+        for _ in range(5):
+            step()
+        torch.cuda.synchronize()
+        lib.eks_profile_enable(0)
+        prof = {k: float(np.mean(v)) for k, v in drain_profile(lib).items()}
     narrow = K <= 16
     longest = max(prof, key=prof.get) if prof else None
     bytes_per_unit = 4 * O * 2 + 4 * D + 4 * D * D           # y, var in; ms, Vs out: 80 B at D = 3, O = 4
@@ -347,17 +405,18 @@ def bench_dense(args, T, K, dev, rank, world, lib, grad=False):
            'data': 'synthetic',
            'config': {'workload': (f'multicam linear T={T} x K={K} keypoints, D={D}, O={O}, ' +
                                    ('constant-R filter NLL and d/d log s at s=10 (the Adam loop body)' if grad
-                                    else 'fixed s=10, full ms/Vs'))},
-           'roofline': {'bound': 'hbm', 'kernel': 'whole step (' + ' + '.join(sorted(prof)) + ')', 'unit': 'GB/s',
-                        'peak': HBM_PEAK_GBS, 'achieved': whole, 'frac': whole / HBM_PEAK_GBS, 'traffic': None,
-                        'algorithmic_bytes_per_unit': bytes_per_unit, 'stage_avg_ms': prof,
-                        'longest_stage': longest,
-                        'note': ('depth-bound: 4 keypoints x 3 125 chunks = 196 workgroups of dependent float64 3x3 '
-                                 'algebra; the bytes (16 MB) are irrelevant, the fraction is reported for the record'
-                                 if narrow else
-                                 'float64 3x3 algebra per frame (about 800 FMAs per keypoint-frame through summarize, '
-                                 'scan and replay) against 80 B: the FP64 vector rate (78.6 TFLOP/s peak) bounds this '
-                                 'shape at about the same level as HBM does')}}
+                                    else 'fixed s=10, full ms/Vs'))}}
+    if prof:
+        out['roofline'] = {'bound': 'hbm', 'kernel': 'whole step (' + ' + '.join(sorted(prof)) + ')', 'unit': 'GB/s',
+                           'peak': HBM_PEAK_GBS, 'achieved': whole, 'frac': whole / HBM_PEAK_GBS, 'traffic': None,
+                           'algorithmic_bytes_per_unit': bytes_per_unit, 'stage_avg_ms': prof,
+                           'longest_stage': longest,
+                           'note': ('depth-bound: 4 keypoints x 3 125 chunks = 196 workgroups of dependent float64 '
+                                    '3x3 algebra; the bytes (16 MB) are irrelevant, the fraction is reported for the '
+                                    'record' if narrow else
+                                    'float64 3x3 algebra per frame (about 800 FMAs per keypoint-frame through '
+                                    'summarize, scan and replay) against 80 B: the FP64 vector rate (78.6 TFLOP/s peak) '
+                                    'bounds this shape at about the same level as HBM does')}
     parity_failed = False
     if not grad and not args.no_cpu_baseline:
         # the timed path's outputs against the float64 C port (oracle/eks_oracle.c: eksc_smooth, the general-matrix
@@ -427,12 +486,14 @@ def bench_c3adam(args, T, K, dev, lib, ranks_info):
         region_dt.append(time.perf_counter() - t0)
     dt = float(np.median(region_dt))
     ms_step = 1e3 * dt / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'s': (last['s'], None), 'ms': (last['ms'], 1), 'Vs': (last['Vs'], 1)}, T)
     st = last['info']['state'].cpu().numpy()
     iters = st[:, 4]
     # per-launch durations of the loss kernel: one extra, untimed step with every launch bracketed by HIP events
     # (288 event records per step would perturb a launch-bound loop inside the timed region)
     prof = {}
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         lib.eks_profile_enable(1)
         step()
         torch.cuda.synchronize()
@@ -590,6 +651,8 @@ def bench_pupil(args, T, dev, lib):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     lib.eks_profile_enable(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'nll': (loss.nll, None), 'dnll': (loss.dnll, None), 'state': (state, None)}, T)
     prof = {k: float(np.mean(v)) for k, v in drain_profile(lib).items()}
     # (dual-number form: one 'ar1_nll' scope; smoothing-distribution form: the wave kernels' two scopes)
     nll_ms = prof['ar1_nll'] if 'ar1_nll' in prof else (sum(prof.values()) if prof else None)
@@ -638,11 +701,13 @@ def bench_ekf(args, T, K, dev, lib, V=4):
     cold = m0[:, None, :].expand(K, T, 3).contiguous()
     xlin = cold.clone()
     info = None
+    last = {}
 
     def step():
         nonlocal info
         xlin.copy_(cold)
-        info = hip_ops.ekf_smooth(y, var, None, m0, S0, A, Q, s, cams, xlin, max_sweeps=8, tol=1e-10)[3]
+        ms, Vs, nll, info = hip_ops.ekf_smooth(y, var, None, m0, S0, A, Q, s, cams, xlin, max_sweeps=8, tol=1e-10)
+        last.update(ms=(ms, 0), Vs=(Vs, 0), nll=(nll, None))
 
     for _ in range(args.warmup):
         step()
@@ -655,6 +720,8 @@ def bench_ekf(args, T, K, dev, lib, V=4):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     lib.eks_profile_enable(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, T)
     prof = {k: float(np.mean(v)) for k, v in drain_profile(lib).items()}
     O = 2 * V
     bytes_per_unit = 4 * O * 2 + 4 * 3 + 4 * 9            # y, var in; ms, Vs out (float32)
@@ -830,9 +897,12 @@ def main():
         sync()
         region_dt.append(time.perf_counter() - t0)
     lib.eks_profile_enable(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'s': (s_last, None), 'ms': (ms, 0), 'Vs': (Vs, 0)}, T,
+                     f'_rank{rank}' if world > 1 else '')
     prof = drain_profile(lib) if region_events else {}
     stages = {}
-    if events_on and rank == 0:
+    if events_on and args.full and rank == 0:
         lib.eks_profile_enable(1)
         for _ in range(5):
             step()
@@ -842,7 +912,7 @@ def main():
         stages = {k: float(np.mean(v)) for k, v in raw.items()}
         if not region_events:
             prof = raw
-    elif events_on and use_dist:
+    elif events_on and args.full and use_dist:
         for _ in range(5):          # keep the ranks' collectives matched
             step()
         sync()
@@ -923,11 +993,13 @@ def main():
                 'stage_avg_ms_source': 'HIP events, 5 untimed steps after the timed region',
                 'smooth_stage_frac': SMOOTH_BYTES_PER_UNIT * local_units / (smooth_ms * 1e-3)
                                      / 1e9 / HBM_PEAK_GBS,
+            } if stages else {}                        # (the untimed stage pass runs under --full only)
+            stage_info.update({
                 'whole_step_frac': ((SMOOTH_BYTES_PER_UNIT + (NLL_BYTES_PER_UNIT if n_cand else 0))
                                     * local_units / (dt / args.steps) / 1e9 / HBM_PEAK_GBS),
                 'whole_step_algorithmic_bytes': (SMOOTH_BYTES_PER_UNIT + (NLL_BYTES_PER_UNIT if n_cand else 0))
                                                 * local_units,
-            }
+            })
             nll_live = prof.get('diag_nll_summarize', [])
             if n_cand and nll_live:
                 # the DOMINANT (longest) kernel of the step is not HBM-bound: 2 FMAs per frame, chain and
@@ -1056,8 +1128,8 @@ def collect_extras(budget_s=75.0, per_leg_s=45.0):
             continue
         t0 = time.perf_counter()
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--workload', wl, '--no-extras'] + extra,
-                               capture_output=True, text=True, timeout=min(per_leg_s, left))
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--workload', wl, '--full', '--no-extras']
+                               + extra, capture_output=True, text=True, timeout=min(per_leg_s, left))
             line = [ln for ln in r.stdout.splitlines() if ln.lstrip().startswith('{')]
             if not line:
                 extras[wl] = {'failed': f'exit code {r.returncode}', 'stderr_tail': r.stderr[-300:]}
@@ -1083,8 +1155,8 @@ def collect_extras(budget_s=75.0, per_leg_s=45.0):
             extras[wl] = {'failed': f'no line within {min(per_leg_s, left):.0f} s'}
         except Exception as ex:                        # noqa: BLE001 - the headline line must go out
             extras[wl] = {'failed': repr(ex)}
-    extras['note'] = ('short legs run after the headline was timed, one child process each (`--workload X --no-extras`); '
-                      'never part of `value`; c3adam = BASELINE configs[2] in the reference\'s default mode (Adam on log s)')
+    extras['note'] = ('short legs run after the headline was timed, one child process each '
+                      '(`--workload X --full --no-extras`); never part of `value`; c3adam = BASELINE configs[2] in the reference\'s default mode (Adam on log s)')
     return extras
 
 

@@ -94,9 +94,7 @@ def test_reader_dtypes_blank_lines_crlf_and_the_fallback(tmp_path):
 def test_reader_equals_pandas_on_the_reference_recordings(golden_dir, tmp_path):
     """tests/golden/csv_samples.npz (tools/make_golden.py csv) keeps the header rows and the first 40 / last 5 lines of
     every recording under the reference's data/ - data files of its own tests - with the values pandas read from them
-    in the build container: the reader returns those bits, and what pandas returns here.  In the build container the
-    whole recordings are compared as well."""
-    import glob
+    when the fixture was made: the reader returns those bits, and what pandas returns here."""
     g = np.load(os.path.join(golden_dir, 'csv_samples.npz'))          # plain arrays: the texts are bytes + offsets
     assert len(g['names']) >= 30
     raw, offs = g['texts_bytes'].tobytes(), g['texts_offsets']
@@ -111,9 +109,6 @@ def test_reader_equals_pandas_on_the_reference_recordings(golden_dir, tmp_path):
         assert np.array_equal(a.view(np.int64)[~np.isnan(a)], b.view(np.int64)[~np.isnan(b)]), name
         assert np.array_equal(np.isnan(a), np.isnan(b)), name
         _same(p)
-    if os.path.isdir('/root/reference/data'):
-        for f in sorted(glob.glob('/root/reference/data/**/*.csv', recursive=True)):
-            _same(f)
 
 
 @pytest.mark.parametrize('with_nan', [False, True])
