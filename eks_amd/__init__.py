@@ -18,6 +18,7 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'fit_eks_multicam_ibl_paw': 'ibl_paw_multicam_smoother',
         'fit_eks_pupil': 'ibl_pupil_smoother', 'ensemble_kalman_smoother_ibl_pupil': 'ibl_pupil_smoother',
         'run_kalman_smoother': 'core', 'ensemble': 'core', 'optimize_smooth_param': 'core',
+        'DifferentiableEmission': 'emission',
     }
     if name in table:
         return getattr(importlib.import_module(f'.{table[name]}', __name__), name)

@@ -462,6 +462,13 @@ def optimize_smooth_param(ys, m0s, S0s, As, Cs, Qs, Rs, blocks, s_finals, s_fram
     if not blocks:
         blocks = [[k] for k in range(K)]
     Rd = np.diagonal(_to_numpy(Rs), axis1=-2, axis2=-1)                 # (K,T,O)
+    if h_fn_combined is not None and _is_emission(h_fn_combined):   # any differentiable h (reference :478-510)
+        s, _, _, _ = _run_kalman_smoother_emission(
+            ys, m0s, S0s, As, Qs, np.swapaxes(Rd, 0, 1), h_fn_combined, s_frames, None, blocks, lr,
+            s_bounds_log, tol, safety_cap, 'adam', 0, True, True, None,
+            guesses=np.asarray(s_guess_per_k, float), min_R_var=min_R_var, final_pass=False)
+        s_finals[:] = s
+        return
     if h_fn_combined is not None:       # calibrated projection: extended filter (reference :478-510)
         s, _, _ = _run_kalman_smoother_pinhole(
             ys, m0s, S0s, As, Qs, np.swapaxes(Rd, 0, 1), h_fn_combined, s_frames, None, blocks, lr,
@@ -490,8 +497,9 @@ def _run_kalman_smoother_pinhole(ys, m0s, S0s, As, Qs, ensemble_vars, h_fn, s_fr
     from .calibration import PinholeProjection
     if not isinstance(h_fn, PinholeProjection):
         raise NotImplementedError(
-            'h_fn must be an eks_amd.calibration.PinholeProjection (make_projection_from_camgroup): '
-            'the HIP kernels cannot call a Python emission function')
+            'h_fn must be an eks_amd.calibration.PinholeProjection (make_projection_from_camgroup) or an '
+            'eks_amd.emission.DifferentiableEmission wrapping a torch function: the HIP kernels cannot call a '
+            'bare Python callable')
     torch = _torch()
     dev = hip_ops.require_gpu()
     f64 = lambda a: torch.as_tensor(np.ascontiguousarray(_to_numpy(a, np.float64)), device=dev)
@@ -617,6 +625,254 @@ def _warn_if_unconverged(worst: float, lin_tol: float, max_sweeps: int) -> None:
         logger.warning(f'extended filter: linearisation points still moving by {worst:.2e} after '
                        f'{max_sweeps} sweeps (tolerance {lin_tol:.0e}); the result may differ from '
                        'the sequential extended Kalman filter')
+
+
+def _is_emission(h_fn) -> bool:
+    from .emission import DifferentiableEmission
+    return isinstance(h_fn, DifferentiableEmission)
+
+
+# Grid mode replicates the chains once per candidate; the candidates go through in groups whose linearisation tables
+# (8 T O (D + 1) bytes per chain, plus as much again for the evaluation that fills them) stay under this budget.
+_EMISSION_TABLE_BUDGET_BYTES = 1 << 30
+
+
+def _check_emission(h_fn, ys, m0s, x_init):
+    """Host-side validation of a DifferentiableEmission call (before any device work): limits of the generic kernels
+    and one evaluation of fn (and of a supplied jacobian) at the prior means.  Returns (K, T, D, O)."""
+    torch = _torch()
+    m0 = np.asarray(_to_numpy(m0s, np.float64))
+    if m0.ndim != 2:
+        raise ValueError(f'm0s must be (K, D); got shape {m0.shape}')
+    K, D = m0.shape
+    shp = tuple(ys.shape) if hasattr(ys, 'shape') else np.shape(ys)
+    if len(shp) != 3 or shp[0] != K:
+        raise ValueError(f'ys must be (K, T, O) with K = {K}; got shape {shp}')
+    T, O = int(shp[1]), int(shp[2])
+    if not 1 <= D <= 6:
+        raise ValueError(f'state dimension D = {D} is outside 1..6, the limit of the generic kernels')
+    if not 1 <= O <= 64:
+        raise ValueError(f'observation dimension O = {O} is outside 1..64, the limit of the generic kernels')
+    if x_init is not None and tuple(np.shape(x_init)) != (K, T, D):
+        raise ValueError(f'x_init must be (K, T, D) = {(K, T, D)}; got {tuple(np.shape(x_init))}')
+    dev = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+    x = torch.as_tensor(m0, device=dev)
+    h = h_fn.values(x)
+    if not hasattr(h, 'shape') or tuple(h.shape) != (K, O):
+        raise ValueError(f'fn at m0s must return (K, O) = {(K, O)} (O = the last axis of ys); got '
+                         f'{tuple(getattr(h, "shape", ()))}')
+    if not bool(torch.isfinite(h).all()):
+        raise ValueError('fn at m0s returned non-finite values')
+    if h_fn.jacobian is not None:
+        J = h_fn.jacobian(x) if h_fn.batched else torch.func.vmap(h_fn.jacobian)(x)
+        if not hasattr(J, 'shape') or tuple(J.shape) != (K, O, D):
+            raise ValueError(f'jacobian at m0s must return (K, O, D) = {(K, O, D)}; got '
+                             f'{tuple(getattr(J, "shape", ()))}')
+    return K, T, D, O
+
+
+class _EmissionSweeps:
+    """Tabulate the user's function at the linearisation points and run eks_ekf_affine_sweep until the points stop
+    moving.  One instance per (chains, frames) shape; the tables and the workspace are reused across solves."""
+
+    def __init__(self, h_fn, K, T, D, O, dev, want_smoother=False):
+        from .emission import eval_batch_points
+        torch = _torch()
+        self.h_fn, self.K, self.T, self.D, self.O = h_fn, K, T, D, O
+        self.jac = torch.empty((T, K, O, D), dtype=torch.float64, device=dev)
+        self.off = torch.empty((T, K, O), dtype=torch.float64, device=dev)
+        self.ws = hip_ops.ekf_affine_workspace(K, T, D, O, want_smoother, dev)
+        self.nll = torch.empty((K,), dtype=torch.float64, device=dev)
+        self.change = torch.empty((1,), dtype=torch.float64, device=dev)
+        self.batch = eval_batch_points(D, O)
+
+    def evaluate(self, xlin):
+        """fn and its Jacobian at every (frame, chain) point, frame-major: h -> self.off, J -> self.jac."""
+        torch = _torch()
+        X = xlin.transpose(0, 1).reshape(-1, self.D)           # (T K, D), the tables' row order
+        jac, off = self.jac.view(-1, self.O, self.D), self.off.view(-1, self.O)
+        for i in range(0, X.shape[0], self.batch):
+            h, J = self.h_fn.values_and_jacobians(X[i:i + self.batch])
+            jac[i:i + self.batch] = J
+            off[i:i + self.batch] = h
+        return X
+
+    def assemble(self, X):
+        """c = h(X) - J X in place of h."""
+        off = self.off.view(-1, self.O, 1)
+        off.baddbmm_(self.jac.view(-1, self.O, self.D), X.view(-1, self.D, 1), beta=1.0, alpha=-1.0)
+
+    def tabulate(self, xlin):
+        self.assemble(self.evaluate(xlin))
+
+    def sweep(self, y, var, rconst, m0, S0, A, Q, s, xlin, want_smoother=False, vs_diag=False):
+        return hip_ops.ekf_affine_sweep(y, var, rconst, m0, S0, A, Q, s, self.jac, self.off, xlin, want_smoother,
+                                        vs_diag, ws=self.ws, nll=self.nll, change=self.change)
+
+    def solve(self, y, var, rconst, m0, S0, A, Q, s, xlin, max_sweeps, lin_tol, want_smoother=False,
+              vs_diag=False):
+        """Sweeps until the largest relative change of a point is at most lin_tol (one read-back per sweep), then,
+        if asked, the smoothing sweep.  Returns (ms, Vs, nll, sweeps, last change)."""
+        sweeps, change = 0, float('inf')
+        while sweeps < max_sweeps:
+            self.tabulate(xlin)
+            _, _, nll, ch = self.sweep(y, var, rconst, m0, S0, A, Q, s, xlin)
+            sweeps += 1
+            change = float(ch.item())
+            if change <= lin_tol:
+                break
+        ms = Vs = None
+        if want_smoother:
+            # converged at a tight tolerance: the tables of the last sweep ARE the converged ones (rebuilt at the new
+            # points they would differ by ~lin_tol), so the smoothing sweep reuses them (as eks_ekf_smooth does)
+            if not (change <= lin_tol and lin_tol < 1e-8):
+                self.tabulate(xlin)
+                sweeps += 1
+            ms, Vs, nll, ch = self.sweep(y, var, rconst, m0, S0, A, Q, s, xlin, True, vs_diag)
+            if not change <= lin_tol:
+                change = float(ch.item())
+        return ms, Vs, nll, sweeps, change
+
+
+def _run_kalman_smoother_emission(ys, m0s, S0s, As, Qs, ensemble_vars, h_fn, s_frames, smooth_param,
+                                  blocks, lr, s_bounds_log, tol, safety_cap, s_mode, n_grid, vs_diag,
+                                  return_device, x_init, fd_step: float = 1e-3, guesses=None,
+                                  min_R_var: float = 1e-4, final_pass: bool = True):
+    """run_kalman_smoother with a user-supplied differentiable emission function (reference eks/core.py:159-302
+    with h_fn; optimiser :562-699 / :306-559).  The extended filter is the fixed point of eks_ekf_affine_sweep over
+    the linearisation points: torch evaluates h and its Jacobian at the points (all chains and frames in batched
+    calls), the kernels run the linear time-varying filter of those tables and return its predicted means as the
+    next points.  The s search is the pinhole path's: Adam on log s with a central difference over three replicated
+    chains (u, u + h, u - h) that keep their own points between iterations, or a grid of replicated chains.
+    Returns (s_finals, ms, Vs, info)."""
+    K, T, D, O = _check_emission(h_fn, ys, m0s, x_init)
+    lin_tol, max_sweeps = h_fn.lin_tol, h_fn.max_sweeps
+    torch = _torch()
+    dev = hip_ops.require_gpu()
+    f64 = lambda a: torch.as_tensor(np.ascontiguousarray(_to_numpy(a, np.float64)), device=dev)
+    m0, S0, A, Q = f64(m0s), f64(S0s), f64(As), f64(Qs)
+    if hasattr(ys, 'detach'):
+        y = ys.to(dev, dtype=torch.float32).transpose(0, 1).contiguous()
+        var = ensemble_vars.to(dev, dtype=torch.float32).contiguous()
+    else:
+        y = torch.as_tensor(np.ascontiguousarray(_to_numpy(ys)), device=dev).to(torch.float32)
+        y = y.transpose(0, 1).contiguous()
+        var = torch.as_tensor(np.ascontiguousarray(_to_numpy(ensemble_vars)), device=dev)
+        var = var.to(torch.float32).contiguous()
+    if T < 2:                       # reference eks/core.py:233-236 (initial guesses, unconditional)
+        raise ValueError('Not enough frames to compute temporal differences.')
+    if tuple(var.shape) != (T, K, O):
+        raise ValueError(f'ensemble_vars must be (T, K, O) = {(T, K, O)}; got {tuple(var.shape)}')
+    for name, a in (('S0s', S0), ('As', A), ('Qs', Q)):
+        if tuple(a.shape) != (K, D, D):
+            raise ValueError(f'{name} must be (K, D, D) = {(K, D, D)}; got {tuple(a.shape)}')
+    if not blocks:
+        blocks = [[k] for k in range(K)]
+    if x_init is None:
+        xlin = m0[:, None, :].expand(K, T, D).contiguous()
+    else:
+        xlin = f64(x_init).reshape(K, T, D).contiguous()
+    worst, search_sweeps = 0.0, 0
+
+    def crop(a):
+        if not s_frames or (len(s_frames) == 1 and s_frames[0] == (None, None)):
+            return a, None
+        if not isinstance(s_frames, list):
+            raise TypeError('s_frames must be a list of (start, end) tuples or None.')
+        idx = torch.cat([torch.arange(a0, b0, device=dev) for a0, b0 in frame_spans(T, s_frames)])
+        return a.index_select(0, idx).contiguous(), idx
+
+    s_finals = np.empty(K, dtype=float)
+    info = {}
+    if smooth_param is not None:
+        s_finals[:] = float(smooth_param) if isinstance(smooth_param, (int, float)) \
+            else np.asarray(smooth_param, dtype=float)
+        s_dev = torch.as_tensor(s_finals, device=dev)
+    else:
+        y_c, idx = crop(y)
+        Tc = y_c.shape[0]
+        var_c = var if idx is None else var.index_select(0, idx).contiguous()
+        x_c = xlin if idx is None else xlin.index_select(1, idx).contiguous()
+        rconst = hip_ops.const_r(var_c, min_R_var)
+        lo, hi = float(s_bounds_log[0]), float(s_bounds_log[1])
+        offs, members, of_kp = _block_csr(blocks, K)
+        nb = len(blocks)
+        if s_mode == 'grid':
+            cand = torch.exp(torch.linspace(lo, hi, n_grid, dtype=torch.float64, device=dev))
+            per_cand = 2 * 8 * K * Tc * O * (D + 1)
+            g = max(1, min(n_grid, _EMISSION_TABLE_BUDGET_BYTES // max(per_cand, 1)))
+            nll = torch.empty((n_grid, K), dtype=torch.float64, device=dev)
+            runners = {}
+            for c0 in range(0, n_grid, g):
+                c1 = min(n_grid, c0 + g)
+                n = c1 - c0
+                if n not in runners:
+                    runners[n] = _EmissionSweeps(h_fn, n * K, Tc, D, O, dev)
+                rep = lambda a: a.repeat((n,) + (1,) * (a.dim() - 1))
+                xg = x_c.repeat(n, 1, 1)
+                _, _, nll_g, sw, ch = runners[n].solve(y_c, None, rconst, rep(m0), rep(S0), rep(A), rep(Q),
+                                                       cand[c0:c1].repeat_interleave(K).contiguous(), xg,
+                                                       max_sweeps, lin_tol)
+                nll[c0:c1] = nll_g.view(n, K)
+                worst, search_sweeps = max(worst, ch), search_sweeps + sw
+            nll = nll.transpose(0, 1).contiguous()
+            blk = torch.zeros((nb, n_grid), dtype=torch.float64, device=dev)
+            blk.index_add_(0, torch.as_tensor(of_kp, device=dev), nll)
+            s_blk, amin = hip_ops.argmin_s(blk, cand)
+            s_dev = s_blk[torch.as_tensor(of_kp, device=dev)].contiguous()
+            info = dict(mode='grid', nll=nll, argmin=amin, candidates=cand)
+        else:
+            if guesses is None:
+                ev_host = _to_numpy(ensemble_vars)[:2000] if not hasattr(ensemble_vars, 'detach') \
+                    else ensemble_vars[:2000].detach().cpu().numpy()
+                guesses = _initial_guesses_per_keypoint(ev_host)
+            u0 = np.array([np.float32(np.log(np.clip(np.mean([guesses[k] for k in b]), 1e-6, 1e3)))
+                           for b in blocks], dtype=np.float64)
+            state = np.zeros((nb, 6))
+            state[:, 0] = u0
+            state[:, 3] = np.inf
+            state = torch.as_tensor(state, device=dev)
+            offs_d, mem_d = torch.as_tensor(offs, device=dev), torch.as_tensor(members, device=dev)
+            s_kp = torch.as_tensor(np.exp(np.clip(u0, lo, hi))[of_kp], device=dev)
+            n_active = torch.zeros(1, dtype=torch.int32, device=dev)
+            rep3 = lambda a: a.repeat((3,) + (1,) * (a.dim() - 1))
+            m3, S3, A3, Q3 = rep3(m0), rep3(S0), rep3(A), rep3(Q)
+            x3 = x_c.repeat(3, 1, 1)
+            step = torch.tensor([1.0, np.exp(fd_step), np.exp(-fd_step)], dtype=torch.float64, device=dev)
+            runner = _EmissionSweeps(h_fn, 3 * K, Tc, D, O, dev)
+            iters, cap = 0, int(safety_cap)
+            while iters < cap:
+                s3 = (step[:, None] * s_kp[None, :]).reshape(-1).contiguous()
+                # each chain keeps its points between iterations: warm-started solves settle in 1-3 sweeps
+                _, _, nll3, sw, ch = runner.solve(y_c, None, rconst, m3, S3, A3, Q3, s3, x3, max_sweeps, lin_tol)
+                worst, search_sweeps = max(worst, ch), search_sweeps + sw
+                nll3 = nll3.view(3, K)
+                dnll = ((nll3[1] - nll3[2]) / (2.0 * fd_step)).contiguous()
+                hip_ops.adam_step(offs_d, mem_d, nll3[0].contiguous(), dnll, state, s_kp, n_active,
+                                  lr, lo, hi, tol, cap)
+                iters += 1
+                if int(n_active.item()) == 0:
+                    break
+            s_dev = s_kp
+            info = dict(mode='adam', state=state, launches=iters)
+            if idx is None:
+                xlin = x3[:K].contiguous()          # warm start of the final pass
+        info.update(search_sweeps=search_sweeps, search_change=worst)
+        s_finals[:] = s_dev.cpu().numpy()
+        _log_opt(blocks, s_finals, info)
+    if not final_pass:                  # optimize_smooth_param only wants s (reference :306-559)
+        _warn_if_unconverged(worst, lin_tol, max_sweeps)
+        return s_finals, None, None, info
+    runner = _EmissionSweeps(h_fn, K, T, D, O, dev, want_smoother=True)
+    ms, Vs, _, sweeps, change = runner.solve(y, var, None, m0, S0, A, Q, s_dev.contiguous(), xlin, max_sweeps,
+                                             lin_tol, want_smoother=True, vs_diag=vs_diag)
+    worst = max(worst, change)
+    info.update(sweeps=sweeps, change=change, worst_change=worst)
+    _warn_if_unconverged(worst, lin_tol, max_sweeps)
+    if return_device:
+        return s_finals, ms.transpose(0, 1), Vs.transpose(0, 1), info
+    ms_h, Vs_h = _to_host(ms, Vs)
+    return s_finals, np.swapaxes(ms_h, 0, 1), np.swapaxes(Vs_h, 0, 1), info
 
 
 def _log_opt(blocks, s_finals, info) -> None:
@@ -908,9 +1164,18 @@ def run_kalman_smoother(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_frames: list 
     the kernels cannot call back into Python, so any other callable raises NotImplementedError.
     `Cs` is ignored then, D must be 3 and O = 2 * n_cameras.  x_init (K,T,3), optional: a first
     guess of the states (e.g. the triangulated points) that the linearisation starts from.
+    Any other differentiable h goes in as an `emission.DifferentiableEmission` (a torch function of one
+    state (D,) -> (O,)): the same extended smoother with D from m0s (1..6), O from ys (1..64), Cs
+    ignored, x_init (K,T,D); return_info then carries the sweeps run and the last change of a
+    linearisation point.
     """
     if s_mode not in ('adam', 'grid'):
         raise ValueError("s_mode must be 'adam' or 'grid'")
+    if h_fn is not None and _is_emission(h_fn):
+        res = _run_kalman_smoother_emission(ys, m0s, S0s, As, Qs, ensemble_vars, h_fn, s_frames,
+                                            smooth_param, blocks, lr, s_bounds_log, tol, safety_cap,
+                                            s_mode, n_grid, vs_diag, return_device, x_init)
+        return res if return_info else res[:3]
     if h_fn is not None:
         res = _run_kalman_smoother_pinhole(ys, m0s, S0s, As, Qs, ensemble_vars, h_fn, s_frames,
                                            smooth_param, blocks, lr, s_bounds_log, tol, safety_cap,

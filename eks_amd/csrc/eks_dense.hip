@@ -619,6 +619,101 @@ int ekf_smooth(const eks_dims_t& d, int n_data_keypoints, const float* y, const 
   return hip_status(hipGetLastError());
 }
 
+// ---- one sweep of the extended filter for a user-supplied emission function -----------------------
+// Reference: run_kalman_smoother(h_fn=...) (eks/core.py:159-177, :188-190) for any differentiable h.  A kernel
+// cannot call the user's (Python) function, so the host tabulates its linearisation at the points X of the
+// sweep (AffineObs: J [T][K][O][D], c = h(X) - J X [T][K][O]) and this runs the linear time-varying filter of
+// those tables on the generic kernels: elements, the two-level scan, then the replay, which writes the
+// filter's predicted means back into xlin (the next sweep's X) and the largest relative change of a point.
+// The host repeats tabulate + sweep until the change is below its tolerance (eks_amd/core.py); at that fixed
+// point the result is the sequential extended filter.  With the tables fixed the scan is exact, so the number
+// of sweeps does not depend on the frames per lane and the chunk length is chosen for the cost of a sweep.
+static int affine_chunk(int T, int K) { return dense_chunk(T, K); }
+
+static size_t affine_ws_layout(int T, int K, int D, bool smooth, double** ptrs, char* base) {
+  const int B = affine_chunk(T, K), nc = (T + B - 1) / B;
+  const int nblk = (nc + kDenseCB - 1) / kDenseCB;
+  const size_t nv = 3 * D * D + 2 * D + 1, rec = D + D * D;
+  const size_t sizes[10] = {(size_t)nc * K * nv * 8,   (size_t)nc * K * nv * 8,
+                            (size_t)nc * K * nv * 8,   (size_t)nblk * K * nv * 8,
+                            (size_t)nblk * K * rec * 8, (size_t)nblk * K * rec * 8,
+                            smooth ? (size_t)T * K * rec * 8 : 0, (size_t)K * rec * 8,
+                            (size_t)nc * K * 8,         8};
+  size_t off = 0;
+  for (int i = 0; i < 10; ++i) {
+    if (ptrs) ptrs[i] = reinterpret_cast<double*>(base + off);
+    off += align_up(sizes[i], 256);
+  }
+  return off;
+}
+
+size_t ekf_affine_workspace_bytes(int T, int K, int D, int smooth) {
+  return affine_ws_layout(T, K, D, smooth != 0, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(64) void affine_finish_kernel(int K, int nc, const double* __restrict__ ll_chunk,
+                                                          const double* __restrict__ resid,
+                                                          double* __restrict__ nll, double* __restrict__ change) {
+  const int k = blockIdx.x, i = threadIdx.x;
+  double acc = 0.0;
+  for (int j = i; j < nc; j += 64) acc += ll_chunk[(size_t)j * K + k];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if (i == 0) {
+    if (nll) nll[k] = -acc;
+    if (k == 0 && change) change[0] = resid[0];
+  }
+}
+
+int ekf_affine_sweep(const eks_dims_t& d, int n_data_keypoints, const float* y, const float* var,
+                     const double* rconst, const DenseModel& Mm, const double* jac, const double* off,
+                     double* xlin, float* ms, float* Vs, double* nll, double* change, void* ws, size_t ws_bytes,
+                     hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim, Kd = n_data_keypoints;
+  if (D < 1 || D > 6 || O < 1 || O > 64 || Kd < 1 || K % Kd != 0) return EKS_ERR_UNSUPPORTED;
+  if (jac == nullptr || off == nullptr) return EKS_ERR_SHAPE;
+  if ((var == nullptr) == (rconst == nullptr)) return EKS_ERR_SHAPE;
+  const bool smooth = ms != nullptr;
+  if (ws_bytes < ekf_affine_workspace_bytes(T, K, D, smooth)) return EKS_ERR_WORKSPACE;
+  double* w[10];
+  affine_ws_layout(T, K, D, smooth, w, static_cast<char*>(ws));
+  double *elems = w[0], *pre = w[1], *suf = w[2], *agg = w[3], *bprior = w[4], *bsuffix = w[5],
+         *filt = w[6], *first = w[7], *ll_chunk = w[8], *resid = w[9];
+  DenseGeom G{K, T, O, affine_chunk(T, K), 0, 0, 0};
+  G.nc = (T + G.B - 1) / G.B;
+  G.Bs = G.B;
+  G.ncs = G.nc;
+  const int nblk = (G.nc + kDenseCB - 1) / kDenseCB, lanes = K * G.nc;
+  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, nullptr, Mm.Q};
+  const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
+  const Gate open{nullptr, 0.0};
+  hipError_t e = hipMemsetAsync(resid, 0, 8, st);
+  if (e != hipSuccess) return hip_status(e);
+  EKS_DISPATCH_D(D, {
+    const AffineObs<DD> obs = make_affine_obs<DD>(y, var, rconst, K, Kd, O, jac, off);
+    {
+      ProfScope ps("ekf_affine_summarize", st);
+      hipLaunchKernelGGL((dense_summarize_kernel<DD, AffineObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
+                         Mm.s, obs, elems, first, open);
+    }
+    {
+      ProfScope ps("ekf_affine_scan", st);
+      hipLaunchKernelGGL(dense_scan_kernel<DD>, dim3(K, nblk), dim3(2 * kDenseCB), 0, st, G, elems, pre, suf, agg,
+                         open);
+      hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk, first, agg,
+                         bprior, bsuffix, open);
+    }
+    {
+      ProfScope ps("ekf_affine_replay", st);
+      hipLaunchKernelGGL((dense_replay_kernel<DD, true, AffineObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G,
+                         M, Mm.s, obs, pre, suf, bprior, bsuffix, smooth ? filt : nullptr, ms, Vs, vs_diag, xlin,
+                         ll_chunk, resid, open);
+    }
+  })
+  hipLaunchKernelGGL(affine_finish_kernel, dim3(K), dim3(64), 0, st, K, G.nc, ll_chunk, resid, nll, change);
+  return hip_status(hipGetLastError());
+}
+
 }  // namespace eks
 
 EKS_DEFINE_TOUCH(dense)

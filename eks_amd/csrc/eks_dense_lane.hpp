@@ -220,6 +220,39 @@ struct PinholeObs {
   }
 };
 
+//   AffineObs  : y = J_t x + c_t + v, the linearisation of a user-supplied emission function h
+//                tabulated on the host at the linearisation points X of the sweep (J_t = dh/dx(X_t),
+//                c_t = h(X_t) - J_t X_t): h = J_t[o], y_eff = y - c_t[o].  visit() ignores xl - the
+//                model is fixed for the whole sweep.  Tables per CHAIN, frame-major so that the lanes
+//                of a wave (consecutive chains at the same chunk) read contiguous segments:
+//                  jac [T][K][O][D] float64,  off [T][K][O] float64.
+template <int D>
+struct AffineObs {
+  const float* y;           // [T][Kd][O]
+  ObsNoise R;               // [T][Kd][O] or constant [Kd][O]
+  int K, Kd, O;             // chain k reads the data of keypoint k % Kd
+  const double* jac;        // [T][K][O][D]
+  const double* off;        // [T][K][O]
+  template <typename Fn>
+  EKS_HD void visit(int t, int k, const double* /*xl*/, Fn&& fn) const {
+    const int kd = k % Kd;
+    const size_t row = ((size_t)t * Kd + kd) * O;
+    const size_t trow = ((size_t)t * K + k) * O;
+    for (int o = 0; o < O; ++o) {
+      Vec<double, D> h;
+      const double* jr = jac + (trow + o) * D;
+#pragma unroll
+      for (int i = 0; i < D; ++i) h.a[i] = jr[i];
+      fn(h, (double)y[row + o] - off[trow + o], R.at(row, kd, O, o));
+    }
+  }
+};
+template <int D>
+EKS_HD AffineObs<D> make_affine_obs(const float* y, const float* var, const double* rconst, int K, int Kd, int O,
+                                    const double* jac, const double* off) {
+  return AffineObs<D>{y, ObsNoise{var, rconst}, K, Kd, O, jac, off};
+}
+
 // Measurement update of the belief N(m, P) with frame t of keypoint k, one scalar observation at
 // a time (R_t diagonal).  Returns the frame's log-likelihood when LL is set.
 template <int D, bool LL = false, typename Obs>
@@ -291,7 +324,9 @@ EKS_HD DElem<double, D> dense_smooth_element(const float* __restrict__ y, const 
 // EKF (extended filter, PinholeObs): every frame is linearised at the lane's own predicted mean
 // (what the reference's dynamax filter does), the predicted mean replaces the
 // stored linearisation point and the largest change is returned through `resid`; `ll` receives
-// the chunk's log-likelihood.  ms == nullptr: filter only (no records, no backward pass).
+// the chunk's log-likelihood.  ms == nullptr: filter only (no records, no backward pass).  With
+// AffineObs the same branch runs the linear time-varying filter of the sweep's tables and stores
+// its predicted means: the next sweep's linearisation points.
 // SCORE (linear observations): no outputs; `ll_out` receives the chunk's log-likelihood and `resid_out` its
 // share of d loglik / d log s by Fisher's identity (eks_dense_wave.hip has the formula), including the
 // transition into the chunk's first frame.

@@ -150,6 +150,12 @@ int ekf_smooth(const eks_dims_t& d, int n_data_keypoints, const float* y, const 
                double* xlin, int max_sweeps, double tol, float* ms, float* Vs, double* nll,
                double* info, void* ws, size_t ws_bytes, hipStream_t st);
 
+size_t ekf_affine_workspace_bytes(int T, int K, int D, int smooth);
+int ekf_affine_sweep(const eks_dims_t& d, int n_data_keypoints, const float* y, const float* var,
+                     const double* rconst, const DenseModel& M, const double* jac, const double* off,
+                     double* xlin, float* ms, float* Vs, double* nll, double* change, void* ws, size_t ws_bytes,
+                     hipStream_t st);
+
 size_t ar1_nll_workspace_bytes(int T, int K, int D, int n_tan);
 int ar1_nll(const eks_dims_t& d, const float* y, const float* var, const double* m0,
             const double* S0, const double* C, const double* a, const double* q, const double* da,

@@ -651,3 +651,60 @@ def ekf_smooth(y, var, rconst, m0, S0, A, Q, s, cams, xlin, max_sweeps: int = 16
                             _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, 'eks_ekf_smooth')
     return ms, Vs, nll_k, info
+
+
+def ekf_affine_workspace(K: int, T: int, D: int, O: int, want_smoother: bool, device):
+    """A workspace for eks_ekf_affine_sweep on (K chains, T frames, D, O); reusable across sweeps."""
+    lib = _lib.load()
+    d = _dims(K, T, D, O, 0)
+    return _workspace(lib.eks_ekf_affine_workspace_bytes(ctypes.byref(d), int(want_smoother)), device)
+
+
+def ekf_affine_sweep(y, var, rconst, m0, S0, A, Q, s, jac, off, xlin, want_smoother: bool = False,
+                     vs_diag: bool = False, ws=None, nll=None, change=None):
+    """eks_ekf_affine_sweep: ONE sweep of the extended filter (+ RTS smoother) of a user-supplied emission function,
+    linearised on the host at the points xlin.
+
+    y (T, Kd, O) float32; exactly one of var (T, Kd, O) float32 / rconst (Kd, O) float64; m0 (K, D), S0, A, Q
+    (K, D, D), s (K,) float64 per CHAIN (K a multiple of Kd; chain k reads keypoint k % Kd); tables jac (T, K, O, D)
+    and off (T, K, O) float64 (include/eks_hip.h); xlin (K, T, D) float64 in/out: on return the sweep's predicted
+    means.  ws: a workspace from ekf_affine_workspace (made here when None); nll (K,), change (1,) float64: optional
+    output buffers.  Returns (ms, Vs, nll, change) as device tensors; ms / Vs are None when want_smoother is False."""
+    lib = _lib.load()
+    T, Kd, O = y.shape
+    K, D = m0.shape
+    y = _chk(y, torch.float32, 'y')
+    if (var is None) == (rconst is None):
+        raise ValueError('pass exactly one of var and rconst')
+    if var is not None:
+        var = _chk(var, torch.float32, 'var', (T, Kd, O))
+    else:
+        rconst = _chk(rconst, torch.float64, 'rconst', (Kd, O))
+    m0 = _chk(m0, torch.float64, 'm0', (K, D))
+    S0 = _chk(S0, torch.float64, 'S0', (K, D, D))
+    A = _chk(A, torch.float64, 'A', (K, D, D))
+    Q = _chk(Q, torch.float64, 'Q', (K, D, D))
+    s = _chk(s, torch.float64, 's', (K,))
+    if jac is not None:
+        jac = _chk(jac, torch.float64, 'jac', (T, K, O, D))
+    if off is not None:
+        off = _chk(off, torch.float64, 'off', (T, K, O))
+    if not xlin.is_contiguous():
+        raise ValueError('xlin must be contiguous (it is updated in place)')
+    _chk(xlin, torch.float64, 'xlin', (K, T, D))
+    d = _dims(K, T, D, O, FLAG_VS_DIAG if vs_diag else 0)
+    ms = Vs = None
+    if want_smoother:
+        ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device)
+        Vs = torch.empty((T, K, D) if vs_diag else (T, K, D, D), dtype=torch.float32, device=y.device)
+    if nll is None:
+        nll = torch.empty((K,), dtype=torch.float64, device=y.device)
+    if change is None:
+        change = torch.empty((1,), dtype=torch.float64, device=y.device)
+    if ws is None:
+        ws = ekf_affine_workspace(K, T, D, O, want_smoother, y.device)
+    rc = lib.eks_ekf_affine_sweep(ctypes.byref(d), int(Kd), _ptr(y), _ptr(var), _ptr(rconst), _ptr(m0), _ptr(S0),
+                                  _ptr(A), _ptr(Q), _ptr(s), _ptr(jac), _ptr(off), _ptr(xlin), _ptr(ms), _ptr(Vs),
+                                  _ptr(nll), _ptr(change), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, 'eks_ekf_affine_sweep')
+    return ms, Vs, nll, change

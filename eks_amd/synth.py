@@ -167,3 +167,121 @@ def calibrated_multicam(T: int, K: int, V: int = 3, M: int = 5, seed: int = 0) -
     return dict(markers=markers, latent=lat, cams=cams, cams_packed=packed, y_tko=y_tko,
                 var_tko=var_tko, m0s=m0s, S0s=S0s, As=np.tile(np.eye(3), (K, 1, 1)), Qs=Qs,
                 s=np.exp(rng.uniform(np.log(0.05), np.log(20.0), size=K)))
+
+
+def torch_pinhole(cams_packed):
+    """The calibrated multi-camera projection (calibration.project, packed cameras (V, 32)) restated in torch
+    for ONE state: x (D >= 3,) float64 -> (2V,) pixels of its first three coordinates.  A test model for
+    emission.DifferentiableEmission (the same function the pinhole kernels evaluate natively)."""
+    import torch
+    packed = np.asarray(cams_packed, dtype=np.float64)
+    per_device = {}
+
+    def fn(x):
+        cams = per_device.get(x.device)
+        if cams is None:                                              # the constants follow the argument's device
+            cams = per_device[x.device] = torch.as_tensor(packed, device=x.device)
+        R, t = cams[:, 0:9].reshape(-1, 3, 3), cams[:, 9:12]
+        fx, fy, cx, cy, skew = (cams[:, 12 + i] for i in range(5))
+        k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4 = (cams[:, 17 + i] for i in range(12))
+        Xc = R @ x[:3] + t                                            # (V, 3)
+        u, v = Xc[:, 0] / Xc[:, 2], Xc[:, 1] / Xc[:, 2]
+        r2 = u * u + v * v
+        radial = 1.0 + r2 * (k1 + r2 * (k2 + r2 * (k3 + r2 * (k4 + r2 * (k5 + r2 * k6)))))
+        ud = u * radial + 2 * p1 * u * v + p2 * (r2 + 2 * u * u) + r2 * (s1 + s2 * r2)
+        vd = v * radial + p1 * (r2 + 2 * v * v) + 2 * p2 * u * v + r2 * (s3 + s4 * r2)
+        return torch.stack([fx * ud + skew * vd + cx, fy * vd + cy], dim=-1).reshape(-1)
+    return fn
+
+
+def _pinhole_np(cams_packed, X):
+    """calibration.project of every camera, concatenated, in plain array arithmetic (complex input stays complex:
+    the oracle takes its Jacobians by complex step)."""
+    out = []
+    for cam in np.asarray(cams_packed, dtype=np.float64):
+        R, t = cam[0:9].reshape(3, 3), cam[9:12]
+        fx, fy, cx, cy, skew = cam[12:17]
+        k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4 = cam[17:29]
+        Xc = X @ R.T + t
+        u, v = Xc[..., 0] / Xc[..., 2], Xc[..., 1] / Xc[..., 2]
+        r2 = u * u + v * v
+        radial = 1.0 + r2 * (k1 + r2 * (k2 + r2 * (k3 + r2 * (k4 + r2 * (k5 + r2 * k6)))))
+        ud = u * radial + 2 * p1 * u * v + p2 * (r2 + 2 * u * u) + r2 * (s1 + s2 * r2)
+        vd = v * radial + p1 * (r2 + 2 * v * v) + 2 * p2 * u * v + r2 * (s3 + s4 * r2)
+        out += [fx * ud + skew * vd + cx, fy * vd + cy]
+    return np.stack(out, axis=-1)
+
+
+def emission_problem(model: str, T: int, K: int, seed: int = 0, V: int = 3) -> dict:
+    """Nonlinear observation models for emission.DifferentiableEmission, each with a torch form of one state and
+    a vectorised NumPy form (complex-step safe):
+      'pinhole' D = 3, O = 2V : the calibrated projection of `calibrated_multicam`
+      'quad'    D = 2, O = 3  : [x0 + 0.05 x1^2, 100 sin(x1 / 50), x0 x1 / 100]
+      'cv6'     D = 6, O = 2V : constant-velocity state, pinhole cameras on its position
+      'exp1'    D = 1, O = 2  : [exp(x / 30), x^2 / 50], the latent kept at x >= 12
+    Returns y_tko / var_tko (T, K, O), m0s, S0s, As, Qs, fn (torch, (D,) -> (O,)), jac (torch, (D,) -> (O, D),
+    analytic where short, else None), h_np ((..., D) -> (..., O)), latent (T, K, D)."""
+    import torch
+    rng = np.random.default_rng(seed)
+    if model == 'pinhole':
+        p = calibrated_multicam(T, K, V, seed=seed)
+        return dict(y_tko=p['y_tko'], var_tko=p['var_tko'], m0s=p['m0s'], S0s=p['S0s'], As=p['As'], Qs=p['Qs'],
+                    fn=torch_pinhole(p['cams_packed']), jac=None, latent=p['latent'],
+                    h_np=lambda X, c=p['cams_packed']: _pinhole_np(c, X), cams_packed=p['cams_packed'])
+    if model == 'quad':
+        D = 2
+        lat = np.cumsum(rng.normal(size=(T, K, D)), axis=0) + rng.uniform(-40, 40, size=(1, K, D))
+
+        def h_np(X):
+            return np.stack([X[..., 0] + 0.05 * X[..., 1] ** 2, 100 * np.sin(X[..., 1] / 50),
+                             X[..., 0] * X[..., 1] / 100], axis=-1)
+
+        def fn(x):
+            return torch.stack([x[0] + 0.05 * x[1] ** 2, 100 * torch.sin(x[1] / 50), x[0] * x[1] / 100])
+
+        def jac(x):
+            z = torch.zeros((), dtype=x.dtype, device=x.device)
+            return torch.stack([torch.stack([z + 1.0, 0.1 * x[1]]), torch.stack([z, 2 * torch.cos(x[1] / 50)]),
+                                torch.stack([x[1] / 100, x[0] / 100])])
+        A, Q, S0 = np.eye(D), np.eye(D), np.eye(D) * 25.0
+        m0 = lat[:10].mean(0) + rng.normal(size=(K, D)) * 2
+    elif model == 'cv6':
+        D = 6
+        p = calibrated_multicam(8, 1, V, seed=seed)
+        cams = p['cams_packed']
+        A = np.eye(D)
+        A[:3, 3:] = np.eye(3)
+        Q = np.diag([0.05, 0.05, 0.05, 1.0, 1.0, 1.0])
+        lat = np.zeros((T, K, D))
+        lat[0, :, :3] = rng.uniform(-100, 100, (K, 3))
+        for t in range(1, T):
+            lat[t] = lat[t - 1] @ A.T + rng.normal(size=(K, D)) * np.sqrt(np.diag(Q)) * np.array([1, 1, 1, .3, .3, .3])
+            lat[t, :, 3:] *= 0.98
+        lat[..., :3] = np.clip(lat[..., :3], -400, 400)
+        h_np = lambda X: _pinhole_np(cams, X[..., :3])        # noqa: E731
+        fn = torch_pinhole(cams)
+        jac = None
+        S0 = np.diag([100.0] * 3 + [4.0] * 3)
+        m0 = np.concatenate([lat[:10, :, :3].mean(0), np.zeros((K, 3))], axis=-1) + rng.normal(size=(K, D)) * 2
+    elif model == 'exp1':
+        D = 1
+        lat = np.clip(np.cumsum(rng.normal(size=(T, K, 1)) * 0.5, axis=0) + 20, 12, 80)
+
+        def h_np(X):
+            return np.concatenate([np.exp(X / 30), X ** 2 / 50], axis=-1)
+
+        def fn(x):
+            return torch.cat([torch.exp(x / 30), x ** 2 / 50])
+
+        def jac(x):
+            return torch.stack([torch.exp(x / 30) / 30, 2 * x / 50])
+        A, Q, S0 = np.eye(D), np.eye(D), np.eye(D) * 4.0
+        m0 = lat[:5].mean(0) + 1.0
+    else:
+        raise ValueError(f'unknown emission model {model!r}')
+    O = h_np(lat[:1, :1]).shape[-1]
+    sig = (0.01 + 0.05 * rng.random((T, K, O))) if model == 'exp1' else (0.25 + rng.random((T, K, O)))
+    y = h_np(lat) + rng.normal(size=(T, K, O)) * np.sqrt(sig)
+    tile = lambda a: np.tile(a[None], (K, 1, 1))             # noqa: E731
+    return dict(y_tko=y, var_tko=sig, m0s=np.asarray(m0, np.float64), S0s=tile(S0), As=tile(A), Qs=tile(Q), fn=fn,
+                jac=jac, h_np=h_np, latent=lat)

@@ -259,6 +259,32 @@ int eks_ekf_smooth(const eks_dims_t* dims, int32_t n_data_keypoints, const float
                    float* Vs, double* nll, double* info, void* workspace, size_t workspace_bytes,
                    eks_stream_t stream);
 
+/* ---- ONE sweep of the extended Kalman filter / smoother for a user-supplied differentiable emission
+ * function: run_kalman_smoother(h_fn = any y_t = h(x_t)), eks/core.py:159-177, :188-190.  The kernels
+ * cannot call the user's function; the caller tabulates its linearisation at the current linearisation
+ * points X (xlin) and this runs the linear time-varying filter y_t = J_t x_t + c_t + v_t of those tables:
+ *   jac [T][K][O][D] float64: J_t = dh/dx at X_t, per chain, frame-major;
+ *   off [T][K][O] float64: c_t = h(X_t) - J_t X_t.
+ * Repeating (tabulate at xlin, sweep) until *change <= tol is the fixed point at which the result equals
+ * the sequential extended filter's (eks_amd/core.py drives the loop).  1 <= D <= 6, 1 <= O <= 64.
+ *   dims.n_keypoints = number of CHAINS K; chain k reads the observations of keypoint
+ *   k % n_data_keypoints (as eks_ekf_smooth).  y [T][Kd][O] float32; exactly one of var [T][Kd][O]
+ *   float32 (time-varying R_t = diag(max(var, 1e-12))) and rconst [Kd][O] float64 (constant R).
+ *   m0 [K][D], S0, A, Q [K][D][D], s [K] per chain.
+ *   xlin [K][T][D] float64, in/out: the points the tables were built at; on return the filter's
+ *   predicted means (the next sweep's points; a non-finite prediction keeps the old point).
+ *   ms [T][K][D], Vs [T][K][D][D] (or [T][K][D] with EKS_FLAG_VS_DIAG) float32 smoothed outputs;
+ *   ms == NULL: filter only.  nll [K] = -marginal log-likelihood of the sweep's filter (may be NULL);
+ *   change [1] = largest change of a point relative to max(1, |x|) (may be NULL).
+ * Missing tables: EKS_ERR_SHAPE; D or O outside the limits: EKS_ERR_UNSUPPORTED.
+ * workspace: eks_ekf_affine_workspace_bytes(dims, ms != NULL). --------------------------------- */
+size_t eks_ekf_affine_workspace_bytes(const eks_dims_t* dims, int32_t want_smoother);
+int eks_ekf_affine_sweep(const eks_dims_t* dims, int32_t n_data_keypoints, const float* y,
+                         const float* var, const double* rconst, const double* m0, const double* S0,
+                         const double* A, const double* Q, const double* s, const double* jac,
+                         const double* off, double* xlin, float* ms, float* Vs, double* nll,
+                         double* change, void* workspace, size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- ensemble statistics, eks/core.py:25-101: markers float32 [M][V][T][K][3] (x,y,likelihood)
  * -> stats float32 [V][T][K][5] (x, y, var_x, var_y, likelihood).  avg_mode 0 median / 1 mean,
  * var_mode 0 confidence_weighted_var / 1 var. ------------------------------------------------ */
