@@ -19,6 +19,7 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'fit_eks_pupil': 'ibl_pupil_smoother', 'ensemble_kalman_smoother_ibl_pupil': 'ibl_pupil_smoother',
         'run_kalman_smoother': 'core', 'ensemble': 'core', 'optimize_smooth_param': 'core',
         'DifferentiableEmission': 'emission',
+        'sample_kalman_posterior': 'posterior', 'sample_singlecam': 'posterior',
     }
     if name in table:
         return getattr(importlib.import_module(f'.{table[name]}', __name__), name)

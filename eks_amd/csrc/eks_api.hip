@@ -62,6 +62,54 @@ int eks_smooth(const eks_dims_t* d, const float* y, const float* var, const doub
   return dense_smooth(*d, y, var, M, ms, Vs, workspace, workspace_bytes, st);
 }
 
+int32_t eks_sample_noise_width(const eks_dims_t* d) {
+  if (check_dims(d) != EKS_OK) return 0;
+  return (d->flags & EKS_FLAG_DIAG_MODEL) ? d->state_dim : d->state_dim + d->obs_dim;
+}
+
+size_t eks_sample_workspace_bytes(const eks_dims_t* d, int32_t n_draws) {
+  if (check_dims(d) != EKS_OK || n_draws < 1) return 0;
+  if (d->flags & EKS_FLAG_DIAG_MODEL)
+    return diag_sample_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim, n_draws);
+  if (d->state_dim > 6 || d->obs_dim > 64) return 0;
+  return dense_sample_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim, n_draws);
+}
+
+int eks_sample(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
+               const double* A, const double* C, const double* Q, const double* s, int32_t n_draws, uint64_t seed,
+               int32_t first_keypoint, int32_t first_draw, const float* noise, float* ms, float* draws,
+               void* workspace, size_t workspace_bytes, eks_stream_t stream) {
+  const int rc = check_dims(d);
+  if (rc != EKS_OK) return rc;
+  if (n_draws < 1 || first_keypoint < 0 || first_draw < 0) return EKS_ERR_SHAPE;
+  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s || !draws) return EKS_ERR_NULL;
+  if (!workspace) return EKS_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (d->flags & EKS_FLAG_DIAG_MODEL) {
+    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
+    return diag_sample(*d, y, var, M, n_draws, seed, first_keypoint, first_draw, noise, ms, draws, workspace,
+                       workspace_bytes, st);
+  }
+  const DenseModel M{m0, S0, A, C, Q, s};
+  return dense_sample(*d, y, var, M, n_draws, seed, first_keypoint, first_draw, noise, ms, draws, workspace,
+                      workspace_bytes, st);
+}
+
+int eks_sample_noise(const eks_dims_t* d, int32_t n_draws, uint64_t seed, int32_t first_keypoint, int32_t first_draw,
+                     float* noise, eks_stream_t stream) {
+  const int rc = check_dims(d);
+  if (rc != EKS_OK) return rc;
+  if (n_draws < 1 || first_keypoint < 0 || first_draw < 0) return EKS_ERR_SHAPE;
+  if (!noise) return EKS_ERR_NULL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (d->flags & EKS_FLAG_DIAG_MODEL)
+    return diag_sample_noise(d->n_frames, d->n_keypoints * d->state_dim, d->state_dim, n_draws, seed, first_keypoint,
+                             first_draw, noise, st);
+  if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
+  return dense_sample_noise(d->n_frames, d->n_keypoints, d->state_dim + d->obs_dim, n_draws, seed, first_keypoint,
+                            first_draw, noise, st);
+}
+
 size_t eks_const_r_workspace_bytes(const eks_dims_t* d) {
   if (check_dims(d) != EKS_OK) return 0;
   return const_r_workspace_bytes(d->n_frames, d->n_keypoints * d->obs_dim);

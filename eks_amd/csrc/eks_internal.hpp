@@ -97,6 +97,21 @@ int32_t* nll_ws_tickets(void* ws, int T, int N, int n_cand);   // the tile ticke
 int adam_prepare(int n_blocks, int K, const int32_t* offs, const int32_t* members, int32_t* kp_block,
                  int32_t* counter_a, int32_t* counter_b, hipStream_t st);
 
+// joint posterior sampling (eks_sample.hip: scalar chains; eks_sample_dense.hip: general models)
+size_t diag_sample_workspace_bytes(int T, int N, int n_draws);
+int diag_sample(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, int n_draws, uint64_t seed,
+                int first_keypoint, int first_draw, const float* noise, float* ms, float* draws, void* ws,
+                size_t ws_bytes, hipStream_t st);
+int diag_sample_noise(int T, int N, int D, int n_draws, uint64_t seed, int first_keypoint, int first_draw, float* noise,
+                      hipStream_t st);
+struct DenseModel;
+size_t dense_sample_workspace_bytes(int T, int K, int D, int O, int n_draws);
+int dense_sample(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, int n_draws, uint64_t seed,
+                 int first_keypoint, int first_draw, const float* noise, float* ms, float* draws, void* ws,
+                 size_t ws_bytes, hipStream_t st);
+int dense_sample_noise(int T, int K, int W, int n_draws, uint64_t seed, int first_keypoint, int first_draw, float* noise,
+                       hipStream_t st);
+
 // general small-matrix path (eks_dense.hip)
 struct DenseModel {
   const double *m0, *S0, *A, *C, *Q, *s;

@@ -200,6 +200,58 @@ def smooth(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False, ou
     return PreparedSmooth(y, var, m0, S0, A, C, Q, s, flags, vs_diag, out)()
 
 
+def sample_noise_width(D: int, O: int, flags: int) -> int:
+    """eks_sample_noise_width: standard normals consumed per (draw, frame, keypoint)."""
+    return int(_lib.load().eks_sample_noise_width(ctypes.byref(_dims(1, 1, D, O, flags))))
+
+
+def sample(y, var, m0, S0, A, C, Q, s, n_draws: int, seed: int = 0, flags: int = 0, first_keypoint: int = 0,
+           first_draw: int = 0, noise=None, want_mean: bool = False, out=None):
+    """eks_sample: n_draws joint posterior trajectories.  Returns (draws (n_draws, T, K, D) float32, ms (T, K, D) or
+    None).  noise (n_draws, T, K, W) float32 replaces the generator; out: a preallocated draws tensor."""
+    lib = _lib.load()
+    T, K, O = y.shape
+    D = m0.shape[-1]
+    n_draws = int(n_draws)
+    if n_draws < 1:
+        raise ValueError('n_draws must be at least 1')
+    y = _chk(y, torch.float32, 'y')
+    var = _chk(var, torch.float32, 'var', (T, K, O))
+    m0 = _chk(m0, torch.float64, 'm0', (K, D))
+    S0 = _chk(S0, torch.float64, 'S0', (K, D, D))
+    A = _chk(A, torch.float64, 'A', (K, D, D))
+    C = _chk(C, torch.float64, 'C', (K, O, D))
+    Q = _chk(Q, torch.float64, 'Q', (K, D, D))
+    s = _chk(s, torch.float64, 's', (K,))
+    flags &= ~FLAG_VS_DIAG
+    dims = _dims(K, T, D, O, flags)
+    if noise is not None:
+        noise = _chk(noise, torch.float32, 'noise', (n_draws, T, K, lib.eks_sample_noise_width(ctypes.byref(dims))))
+    draws = torch.empty((n_draws, T, K, D), dtype=torch.float32, device=y.device) if out is None \
+        else _chk(out, torch.float32, 'out', (n_draws, T, K, D))
+    ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device) if want_mean else None
+    ws = _workspace(lib.eks_sample_workspace_bytes(ctypes.byref(dims), n_draws), y.device)
+    rc = lib.eks_sample(ctypes.byref(dims), _ptr(y), _ptr(var), _ptr(m0), _ptr(S0), _ptr(A), _ptr(C), _ptr(Q), _ptr(s),
+                        n_draws, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_keypoint), int(first_draw), _ptr(noise),
+                        _ptr(ms), _ptr(draws), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, 'eks_sample')
+    return draws, ms
+
+
+def sample_noise(T: int, K: int, D: int, O: int, n_draws: int, seed: int = 0, flags: int = 0, first_keypoint: int = 0,
+                 first_draw: int = 0):
+    """eks_sample_noise: the normals eks_sample(seed) generates, (n_draws, T, K, W) float32."""
+    lib = _lib.load()
+    dev = require_gpu()
+    dims = _dims(K, T, D, O, flags & ~FLAG_VS_DIAG)
+    W = lib.eks_sample_noise_width(ctypes.byref(dims))
+    noise = torch.empty((int(n_draws), T, K, W), dtype=torch.float32, device=dev)
+    rc = lib.eks_sample_noise(ctypes.byref(dims), int(n_draws), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_keypoint),
+                              int(first_draw), _ptr(noise), _stream())
+    _lib.check(rc, 'eks_sample_noise')
+    return noise
+
+
 def const_r(var, min_var: float = 1e-4):
     """eks_const_r: (T, K, O) float32 -> (K, O) float64 floored time-median."""
     lib = _lib.load()

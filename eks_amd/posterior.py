@@ -1,0 +1,138 @@
+"""Joint posterior trajectories of the Kalman smoother.
+
+Everything `run_kalman_smoother` returns is a per-frame marginal (ms[t], Vs[t]).  An error bar on anything that spans
+frames or keypoints - speed, path length, the time of a peak, the distance between two paws - needs whole
+trajectories from the smoothing distribution p(x_1..x_T | y_1..y_T); independent draws from N(ms[t], Vs[t]) give
+white-noise paths.  The reference has no counterpart.
+
+    sample_kalman_posterior(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, n_draws, ...) -> (K, n_draws, T, D)
+    sample_singlecam(marker_array, keypoint_names, s_finals, n_draws, ...) -> (n_draws, T, K, 2) in pixels
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Literal
+
+import numpy as np
+
+from . import hip_ops
+
+__all__ = ['sample_kalman_posterior', 'sample_singlecam']
+
+DEFAULT_MEMORY_BUDGET = 2 << 30     # bytes of device memory one group of draws (output + workspace) may take
+
+
+def _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, n_draws, h_fn, first_keypoint, first_draw):
+    if h_fn is not None:
+        raise NotImplementedError('posterior sampling covers linear models; h_fn models are not supported')
+    if int(n_draws) != n_draws or n_draws < 1:
+        raise ValueError('n_draws must be an integer >= 1')
+    if first_keypoint < 0 or first_draw < 0:
+        raise ValueError('first_keypoint and first_draw must be >= 0')
+    shp = tuple(np.shape(ys))
+    if len(shp) != 3:
+        raise ValueError(f'ys must be (K,T,O); got {shp}')
+    K, T, O = shp
+    if len(np.shape(m0s)) != 2 or np.shape(m0s)[0] != K:
+        raise ValueError(f'm0s must be (K,D); got {tuple(np.shape(m0s))}')
+    D = np.shape(m0s)[1]
+    for name, a, want in (('S0s', S0s, (K, D, D)), ('As', As, (K, D, D)), ('Cs', Cs, (K, O, D)), ('Qs', Qs, (K, D, D)),
+                          ('ensemble_vars', ensemble_vars, (T, K, O))):
+        if tuple(np.shape(a)) != want:
+            raise ValueError(f'{name} must be {want}; got {tuple(np.shape(a))}')
+    s = np.broadcast_to(np.asarray(s_finals, dtype=np.float64), (K,)) if np.ndim(s_finals) == 0 \
+        else np.asarray(s_finals, dtype=np.float64)
+    if s.shape != (K,):
+        raise ValueError(f's_finals must be a scalar or (K,); got {s.shape}')
+    return K, T, O, D, np.ascontiguousarray(s)
+
+
+def _host_flags(S0s, As, Cs, Qs) -> int:
+    from .core import _to_numpy
+    return hip_ops.model_flags(*(np.ascontiguousarray(_to_numpy(a, np.float64)) for a in (S0s, As, Cs, Qs)))
+
+
+def draws_per_group(K: int, T: int, D: int, O: int, flags: int, n_draws: int, memory_budget: int) -> int:
+    """Largest number of draws whose output and workspace fit the budget (at least 1)."""
+    from . import _lib
+    lib = _lib.load()
+    dims = _lib.EksDims(K, T, D, O, flags & ~_lib.FLAG_VS_DIAG)
+    g = int(n_draws)
+    while g > 1 and lib.eks_sample_workspace_bytes(ctypes.byref(dims), g) + g * T * K * D * 4 > memory_budget:
+        g = (g + 1) // 2
+    return g
+
+
+def sample_kalman_posterior(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, n_draws: int, *, seed: int = 0,
+                            noise=None, first_keypoint: int = 0, first_draw: int = 0, return_device: bool = False,
+                            return_mean: bool = False, h_fn=None, memory_budget: int = DEFAULT_MEMORY_BUDGET):
+    """n_draws trajectories from p(x_1..x_T | y_1..y_T) of the linear model run_kalman_smoother smooths, at the
+    smoothing parameters s_finals (scalar or (K,)).  Arguments as run_kalman_smoother: ys (K,T,O); m0s (K,D); S0s, As,
+    Qs (K,D,D); Cs (K,O,D); ensemble_vars (T,K,O).  Returns float32 (K, n_draws, T, D), a transposed view of the
+    kernels' (n_draws, T, K, D) buffer (a NumPy array, or a device tensor with return_device); with return_mean also
+    the smoothed mean (K, T, D) of the same pass.
+
+    The normals come from a counter-based generator keyed by `seed` and indexed by (frame, first_keypoint + k,
+    first_draw + d): keypoints [k0, k1) or draws [d0, d1) of a larger problem are reproduced bit for bit by a call on
+    those alone with first_keypoint = k0 / first_draw = d0.  Draws are produced in groups whose output and workspace
+    fit `memory_budget` bytes of device memory, which changes no value.  noise (n_draws, T, K, W) float32 replaces
+    the generator (W = D on diagonal models, D + O otherwise; zeros return the smoothed mean)."""
+    K, T, O, D, s = _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, n_draws, h_fn, first_keypoint,
+                              first_draw)
+    n_draws = int(n_draws)
+    flags = _host_flags(S0s, As, Cs, Qs)
+    W = hip_ops.sample_noise_width(D, O, flags)
+    if noise is not None and tuple(np.shape(noise)) != (n_draws, T, K, W):
+        raise ValueError(f'noise must be {(n_draws, T, K, W)}; got {tuple(np.shape(noise))}')
+    from .core import _DeviceProblem, _to_host, _torch
+    torch = _torch()
+    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
+    s_dev = torch.as_tensor(s, device=P.dev)
+    if noise is not None:
+        noise = torch.as_tensor(noise, device=P.dev).to(torch.float32).contiguous()
+    group = draws_per_group(K, T, D, O, flags, n_draws, memory_budget)
+    out_dev = torch.empty((n_draws, T, K, D), dtype=torch.float32, device=P.dev) if return_device else None
+    out_host = None if return_device else np.empty((n_draws, T, K, D), dtype=np.float32)
+    ms = None
+    for d0 in range(0, n_draws, group):
+        d1 = min(n_draws, d0 + group)
+        dr, m = hip_ops.sample(P.y, P.var, *P.params, s_dev, d1 - d0, seed=seed, flags=P.flags,
+                               first_keypoint=first_keypoint, first_draw=first_draw + d0,
+                               noise=None if noise is None else noise[d0:d1],
+                               want_mean=return_mean and d0 == 0, out=None if out_dev is None else out_dev[d0:d1])
+        if m is not None:
+            ms = m
+        if out_host is not None:
+            out_host[d0:d1] = _to_host(dr)[0]
+    if return_device:
+        draws = out_dev.permute(2, 0, 1, 3)
+        return (draws, ms.transpose(0, 1)) if return_mean else draws
+    draws = np.transpose(out_host, (2, 0, 1, 3))
+    return (draws, np.swapaxes(_to_host(ms)[0], 0, 1)) if return_mean else draws
+
+
+def sample_singlecam(marker_array, keypoint_names: list, s_finals, n_draws: int, *, seed: int = 0,
+                     avg_mode: Literal['mean', 'median'] = 'median',
+                     var_mode: Literal['var', 'confidence_weighted_var'] = 'confidence_weighted_var',
+                     memory_budget: int = DEFAULT_MEMORY_BUDGET) -> np.ndarray:
+    """Posterior trajectories of the single-camera smoother in PIXEL coordinates, (n_draws, T, K, 2) float32.
+    Rebuilds the ensemble, the centring and the prior as ensemble_kalman_smoother_singlecam does and adds the same
+    means back: over many draws the mean approaches that driver's x, y columns and the variance its
+    x_posterior_var, y_posterior_var columns.  s_finals: the smoothing parameters the driver returned."""
+    from .core import ensemble
+    from .singlecam_smoother import initialize_kalman_filter
+    from .utils import center_predictions
+    M, V, T, K, _ = marker_array.shape
+    if V != 1:
+        raise ValueError('sample_singlecam takes a single-view marker array')
+    if len(keypoint_names) != K:
+        raise ValueError(f'{len(keypoint_names)} keypoint names for {K} keypoints')
+    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)
+    _, centered, _, means = center_predictions(ens, quantile_keep_pca=100)
+    stats = np.asarray(ens.array)[0, 0]
+    cen = np.asarray(centered.array)[0, 0]
+    m0s, S0s, As, Qs, Cs = initialize_kalman_filter(centered)
+    draws = sample_kalman_posterior(np.swapaxes(cen, 0, 1), m0s, S0s, As, Cs, Qs, stats[:, :, 2:4], s_finals, n_draws,
+                                    seed=seed, memory_budget=memory_budget)
+    mu = np.asarray(means.array)[0, 0, 0].astype(np.float32)                     # (K,2)
+    return np.ascontiguousarray(np.transpose(draws, (1, 2, 0, 3))) + mu[None, None]

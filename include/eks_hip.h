@@ -77,6 +77,39 @@ int eks_smooth(const eks_dims_t* dims, const float* y, const float* var, const d
                const double* s, float* ms, float* Vs, void* workspace, size_t workspace_bytes,
                eks_stream_t stream);
 
+/* ---- joint posterior trajectories: n_draws draws of x_1..x_T from the smoothing distribution p(x | y) of the model
+ * eks_smooth smooths (same dims, flags, y, var and parameters; EKS_FLAG_VS_DIAG is ignored).  No reference counterpart:
+ * the reference returns the per-frame marginals ms, Vs only (eks/core.py:296-297), which say nothing about how the
+ * uncertainty of frame t is tied to that of frame t + 1.  A draw is ms + e with e a zero-mean draw of the joint
+ * posterior covariance, an affine function of W standard normals per (draw, frame, keypoint):
+ *   scalar chains (EKS_FLAG_DIAG_MODEL): W = D, backward sampling e_t = G_t e_{t+1} + sqrt(Pf_t s q / Pp_{t+1}) z_t in
+ *     the smoother's chunked scan (eks_amd/csrc/eks_sample.hip): y is read twice and var three times per call whatever
+ *     n_draws is, the filtered quantities are shared by all draws;
+ *   general models: W = D + O, Durbin & Koopman's simulation smoother composed from eks_smooth
+ *     (eks_amd/csrc/eks_sample_dense.hip): correct, not tuned - a draw costs a smoothing pass.
+ * The normals come from Philox4x32-10 (key = (seed & 0xffffffff, seed >> 32)) and Box-Muller, with GLOBAL indices
+ * k' = first_keypoint + k, d' = first_draw + d in the counter, so that a draw depends on no launch geometry and a call
+ * on keypoints [k0, k1) / draws [d0, d1) of a larger problem (first_keypoint = k0, first_draw = d0) returns that
+ * problem's normals bit for bit (and, on scalar chains, its draws bit for bit; on general models the draws agree to
+ * the smoother's rounding, the stacked smoothing call being free to organise its kernels by size).  Exact layout (x0..x3 the block's output words):
+ *   scalar chains: counter = (t / 4, k' * D + i, d', 0) for coordinate i; the block serves the four frames
+ *     4 (t / 4) + {0, 1, 2, 3} of that chain: (z_+0, z_+1) = BM(x0, x1), (z_+2, z_+3) = BM(x2, x3);
+ *   general models: counter = (t, k', d', b); the block gives normals w = 4 b .. 4 b + 3 of (draw, frame, keypoint):
+ *     (z_4b, z_4b+1) = BM(x0, x1), (z_4b+2, z_4b+3) = BM(x2, x3); w < D: state noise (chol(S0) at t = 0, chol(s Q)
+ *     after), w >= D: observation noise of output w - D;
+ *   BM(a, b): u = ((a >> 8) + 0.5) 2^-24, v = (b >> 8) 2^-24, r = sqrt(-2 ln u), (r cos 2 pi v, r sin 2 pi v).
+ *   draws float32 [n_draws][T][K][D]; ms float32 [T][K][D] optional (the smoothed mean of the same pass);
+ *   noise float32 [n_draws][T][K][W] optional: used INSTEAD of the generator (all zeros give draws == ms).
+ * eks_sample_noise writes exactly the normals eks_sample would generate.  n_draws < 1: EKS_ERR_SHAPE. -------------- */
+int32_t eks_sample_noise_width(const eks_dims_t* dims);
+size_t eks_sample_workspace_bytes(const eks_dims_t* dims, int32_t n_draws);
+int eks_sample(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,
+               const double* A, const double* C, const double* Q, const double* s, int32_t n_draws, uint64_t seed,
+               int32_t first_keypoint, int32_t first_draw, const float* noise, float* ms, float* draws,
+               void* workspace, size_t workspace_bytes, eks_stream_t stream);
+int eks_sample_noise(const eks_dims_t* dims, int32_t n_draws, uint64_t seed, int32_t first_keypoint,
+                     int32_t first_draw, float* noise, eks_stream_t stream);
+
 /* ---- constant observation noise for the loss: eks/core.py:702-709
  * rconst[k][o] = max(nanmedian_t max(var[t][k][o], 1e-12), min_var)  (float64 out) ----------- */
 size_t eks_const_r_workspace_bytes(const eks_dims_t* dims);
