@@ -72,6 +72,7 @@ size_t eks_sample_workspace_bytes(const eks_dims_t* d, int32_t n_draws) {
   if (d->flags & EKS_FLAG_DIAG_MODEL)
     return diag_sample_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim, n_draws);
   if (d->state_dim > 6 || d->obs_dim > 64) return 0;
+  if (((size_t)n_draws + 1) * d->n_keypoints * d->state_dim > (1u << 24)) return 0;   // eks_sample: EKS_ERR_SHAPE
   return dense_sample_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim, n_draws);
 }
 
@@ -105,6 +106,7 @@ int eks_sample_noise(const eks_dims_t* d, int32_t n_draws, uint64_t seed, int32_
   if (d->flags & EKS_FLAG_DIAG_MODEL)
     return diag_sample_noise(d->n_frames, d->n_keypoints * d->state_dim, d->state_dim, n_draws, seed, first_keypoint,
                              first_draw, noise, st);
+  if (d->state_dim + d->obs_dim > 6 + 64) return EKS_ERR_SHAPE;   // wider than any supported model's W = D + O
   if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
   return dense_sample_noise(d->n_frames, d->n_keypoints, d->state_dim + d->obs_dim, n_draws, seed, first_keypoint,
                             first_draw, noise, st);

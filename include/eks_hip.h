@@ -100,7 +100,10 @@ int eks_smooth(const eks_dims_t* dims, const float* y, const float* var, const d
  *   BM(a, b): u = ((a >> 8) + 0.5) 2^-24, v = (b >> 8) 2^-24, r = sqrt(-2 ln u), (r cos 2 pi v, r sin 2 pi v).
  *   draws float32 [n_draws][T][K][D]; ms float32 [T][K][D] optional (the smoothed mean of the same pass);
  *   noise float32 [n_draws][T][K][W] optional: used INSTEAD of the generator (all zeros give draws == ms).
- * eks_sample_noise writes exactly the normals eks_sample would generate.  n_draws < 1: EKS_ERR_SHAPE. -------------- */
+ * eks_sample_noise writes exactly the normals eks_sample would generate.  n_draws < 1: EKS_ERR_SHAPE.  General
+ * models: D > 6 or O > 64 is EKS_ERR_UNSUPPORTED, (n_draws + 1) K D > 2^24 (the stacked smoothing call's chains)
+ * EKS_ERR_SHAPE, and eks_sample_workspace_bytes returns 0 for both; eks_sample_noise refuses W = D + O > 70, wider
+ * than any supported model, with EKS_ERR_SHAPE.  Every refusal is returned before anything is enqueued. ------------ */
 int32_t eks_sample_noise_width(const eks_dims_t* dims);
 size_t eks_sample_workspace_bytes(const eks_dims_t* dims, int32_t n_draws);
 int eks_sample(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,

@@ -1,7 +1,8 @@
 """Float64 NumPy reference of the posterior sampler (TEST INFRASTRUCTURE, imported by the sampling tests only):
 Philox4x32-10 and the Box-Muller transform the kernels use, the sequential scalar filter and the backward-sampling
 recurrence, a float32 transcription of that recurrence (what plain float32 arithmetic reaches: it sets the float32
-bars), and the dense joint posterior covariance of a short session by plain linear algebra."""
+bars), the dense joint posterior covariance of a short session by plain linear algebra, and Durbin & Koopman's
+simulation smoother for general models with its float32-storage transcription (dense_durbin_koopman)."""
 from __future__ import annotations
 
 import numpy as np
@@ -148,3 +149,99 @@ def law_error(Lmat, S):
     """max |(L L' - S)_ij| / sqrt(S_ii S_jj)"""
     sd = np.sqrt(np.diag(S))
     return float(np.max(np.abs(Lmat @ Lmat.T - S) / np.outer(sd, sd)))
+
+
+def chol_psd(M):
+    """Lower Cholesky factors of symmetric PSD matrices [K][D][D] by the kernels' documented rule: a non-positive
+    pivot gives a zero column (a singular Q draws nothing along that direction)."""
+    M = np.asarray(M, np.float64)
+    K, D, _ = M.shape
+    L = np.zeros_like(M)
+    for j in range(D):
+        dj = M[:, j, j] - (L[:, j, :j] ** 2).sum(axis=1)
+        ok = dj > 0.0
+        r = np.sqrt(np.where(ok, dj, 1.0))
+        L[:, j, j] = np.where(ok, r, 0.0)
+        for i in range(j + 1, D):
+            v = M[:, i, j] - (L[:, i, :j] * L[:, j, :j]).sum(axis=1)
+            L[:, i, j] = np.where(ok, v / r, 0.0)
+    return L
+
+
+def filter_by_scalar_updates(y, m0, S0, A, C, Q, s, R):
+    """float64 Kalman filter, update-then-predict as oracle.eks_oracle.kalman_filter (frame 0 updates the prior), with
+    the O observations of a frame absorbed one at a time - exact for the diagonal R of this project, and free of the
+    O x O inverse of the innovation covariance.  kalman_filter forms np.linalg.inv(S) and P - K S K': with one variance
+    of a frame at the 1e30 clip and the others near one, cond(S) ~ 1e30, and its means around that frame are off by up
+    to 7e-5 of the chain's largest |ms| in float64 (against the information-form smoother of the oracle and against
+    this filter, which agree); where a frame's variances lie within a few decades the two filters agree to rounding
+    (tests/test_sampling_cpu.py).  y, R (K, T, O); m0 (K, D); S0, A, Q (K, D, D); C (K, O, D); s (K,).
+    Returns mf (K, T, D), Pf (K, T, D, D)."""
+    y, R, m0, S0, A, C, Q = (np.asarray(a, np.float64) for a in (y, R, m0, S0, A, C, Q))
+    K, T, O = y.shape
+    D = m0.shape[-1]
+    sQ = np.broadcast_to(np.asarray(s, np.float64), (K,))[:, None, None] * Q
+    At = np.swapaxes(A, -1, -2)
+    mf, Pf = np.empty((K, T, D)), np.empty((K, T, D, D))
+    m, P = m0.copy(), S0.copy()
+    for t in range(T):
+        if t:
+            m = np.einsum('kij,kj->ki', A, m)
+            P = A @ P @ At + sQ
+        for o in range(O):
+            h = C[:, o]
+            u = np.einsum('kij,kj->ki', P, h)
+            g = 1.0 / (R[:, t, o] + np.einsum('ki,ki->k', h, u))
+            m = m + u * (g * (y[:, t, o] - np.einsum('ki,ki->k', h, m)))[:, None]
+            P = P - u[:, :, None] * u[:, None, :] * g[:, None, None]
+        P = 0.5 * (P + np.swapaxes(P, -1, -2))
+        mf[:, t], Pf[:, t] = m, P
+    return mf, Pf
+
+
+def dense_durbin_koopman(y, var, m0, S0, A, C, Q, s, z, storage=np.float64, round_output=True):
+    """Durbin & Koopman's simulation smoother as eks_sample composes it for general models, a plain sequential
+    construction in float64: y, var [T][K][O]; m0 [K][D]; S0, A, Q [K][D][D]; C [K][O][D]; s [K];
+    z [n_draws][T][K][D + O] (D state normals - chol(S0) at frame 0, chol(s Q) afterwards - then O observation
+    normals).  x+ / y+ are simulated from the zero-mean model with the data's variances clipped to
+    [VAR_FLOOR, VAR_CEIL], the data and every y+ are smoothed by a float64 filter (filter_by_scalar_updates) and the
+    RTS pass of oracle.eks_oracle, and dev = x+ - E[x+ | y+].  Returns ms [T][K][D], Vs [T][K][D][D], dev [n_draws][T][K][D].
+
+    storage = np.float32 is the float32-storage transcription: the same code with x+, y+, the stacked means and the
+    final ms + dev rounded to float32 where the kernels store float32 (dev is then read back off that output as
+    (ms + dev) - ms; round_output = False leaves the last rounding out).  Everything else stays float64."""
+    from oracle.eks_oracle import rts_smoother
+    st = storage
+    y = np.asarray(y, np.float64)
+    var = np.clip(np.asarray(var, np.float64), VAR_FLOOR, VAR_CEIL)
+    T, K, O = y.shape
+    A, C, Q, S0 = (np.asarray(a, np.float64) for a in (A, C, Q, S0))
+    m0 = np.asarray(m0, np.float64)
+    s = np.broadcast_to(np.asarray(s, np.float64), (K,))
+    z = np.asarray(z, np.float64)
+    n, D = z.shape[0], A.shape[-1]
+    assert z.shape == (n, T, K, D + O)
+    L0, Lq = chol_psd(S0), chol_psd(s[:, None, None] * Q)
+    xs = np.empty((n, T, K, D))
+    x = np.zeros((n, K, D))
+    for t in range(T):                                     # the recursion itself runs on the unrounded state
+        x = np.einsum('kij,nkj->nki', L0, z[:, 0, :, :D]) if t == 0 else \
+            np.einsum('kij,nkj->nki', A, x) + np.einsum('kij,nkj->nki', Lq, z[:, t, :, :D])
+        xs[:, t] = x
+    yp = np.einsum('koj,ntkj->ntko', C, xs) + np.sqrt(var)[None] * z[..., D:]
+    xs, yp = xs.astype(st).astype(np.float64), yp.astype(st).astype(np.float64)
+    # one stacked problem of (n + 1) K chains: set 0 the data, set 1 + d the simulated observations with m0 = 0
+    rep = lambda a: np.tile(a, (n + 1,) + (1,) * (a.ndim - 1))
+    y_all = np.concatenate([y[None], yp]).transpose(0, 2, 1, 3).reshape((n + 1) * K, T, O)
+    R_all = np.tile(var.transpose(1, 0, 2), (n + 1, 1, 1))
+    m0_all = np.concatenate([m0, np.zeros((n * K, D))])
+    mf, Pf = filter_by_scalar_updates(y_all, m0_all, rep(S0), rep(A), rep(C), rep(Q), rep(s), R_all)
+    ms_all, Vs_all = rts_smoother(mf, Pf, rep(A), rep(Q), rep(s))
+    ms = ms_all[:K].transpose(1, 0, 2)
+    Vs = Vs_all[:K].transpose(1, 0, 2, 3)
+    mp = ms_all[K:].reshape(n, K, T, D).transpose(0, 2, 1, 3)
+    ms_st, mp = ms.astype(st).astype(np.float64), mp.astype(st).astype(np.float64)
+    dev = xs - mp
+    if round_output and st is not np.float64:
+        dev = (ms_st[None] + dev).astype(st).astype(np.float64) - ms_st[None]
+    return ms_st, Vs, dev

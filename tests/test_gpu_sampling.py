@@ -14,7 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sampling_ref as ref  # noqa: E402
-from test_sampling_cpu import dev_error, make_chains, unit_noise  # noqa: E402
+from test_sampling_cpu import dense_model, dev_error, make_chains, unit_noise  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -80,21 +80,11 @@ def test_exact_law_on_a_short_session_scalar_chains(unit):
     assert worst < bar
 
 
-def dense_model(K, D, O, seed):
-    rng = np.random.default_rng(seed)
-    A = np.eye(D) * 0.95 + 0.05 * rng.normal(size=(K, D, D)) / np.sqrt(D)
-    C = rng.normal(size=(K, O, D))
-    Lq = rng.normal(size=(K, D, D)) * 0.4 + np.eye(D)
-    Q = Lq @ np.swapaxes(Lq, 1, 2)                                   # non-diagonal, positive definite
-    L0 = rng.normal(size=(K, D, D)) * 0.3 + 1.5 * np.eye(D)
-    S0 = L0 @ np.swapaxes(L0, 1, 2)
-    return dict(m0=rng.normal(size=(K, D)), S0=S0, A=A, C=C, Q=Q, s=rng.uniform(0.5, 2.0, K))
-
-
 @pytest.mark.parametrize('D,O', [(3, 4), (5, 6)])
 def test_exact_law_on_a_short_session_dense_models(D, O):
-    """Durbin-Koopman path through eks_amd.posterior.  No float32 transcription exists for this path, so the bar is
-    the project's 1e-5 as it stands (measured on the MI355X: 2.1e-7 at D = 3, O = 4 and 2.6e-7 at D = 5, O = 6)."""
+    """Durbin-Koopman path through eks_amd.posterior.  The bar is the project's 1e-5 as it stands (measured on the
+    MI355X: 2.1e-7 at D = 3, O = 4 and 2.6e-7 at D = 5, O = 6); the float32-storage transcription of this path
+    (ref.dense_durbin_koopman) sets the bars of tests/test_gpu_sampling_dense.py."""
     from eks_amd import hip_ops
     from eks_amd.posterior import sample_kalman_posterior
     T, K = 12, 3
@@ -149,6 +139,84 @@ def test_same_noise_parity_with_the_float64_reference_at_size(T, K, unit, sval):
                              *(_dev(par[k]) for k in ('m0', 'S0', 'A', 'C', 'Q', 's')), flags=_flags(pb), vs_diag=True)
     ms_s = ms_s.cpu().numpy().reshape(T, -1)
     assert (np.abs(ms - ms_s) / np.abs(ms_s).max(axis=0)).max() < 1e-5
+
+
+# N = K D chains against the lane mapping of sample_coords (eks_sample.hip): 2^nt_log2 = min(64, pow2ceil(N)) chains
+# per wave row, so N = 1, 3, 6 put 64, 16, 8 chunks of one chain side by side in a wave (with idle lanes at N = 3, 6);
+# N = 63 leaves one lane of every row idle; N = 65, 130, 195 have a ragged last tile of 1, 2, 3 chains.
+EDGE_CHAINS = [(1, 1), (3, 1), (1, 3), (3, 2), (21, 3), (63, 1), (65, 1), (65, 2), (65, 3)]
+# T against the 32-frame chunks and the two-level scan groups gs = ceil(sqrt(nc)): 1, 2, 3 frames; one chunk short of /
+# exactly / past a chunk edge; nc = 32 -> 33 at T = 1024 -> 1025 (gs = 6, six groups, the last of two -> three chunks);
+# nc = 31 = gs^2 - gs + 1 at T = 32 x 30 + 5 (the last group holds a single, partial chunk) and nc = 32 at
+# T = 32 x 31 + 5 (the last group holds two chunks of six, the second partial).
+EDGE_FRAMES = [1, 2, 3, 31, 32, 33, 965, 997, 1024, 1025]
+
+
+@pytest.mark.parametrize('T', EDGE_FRAMES)
+@pytest.mark.parametrize('K,D', EDGE_CHAINS)
+def test_scalar_chain_edge_shapes_injected_noise_and_generator(K, D, T):
+    """Unit and non-unit chains.  Injected normals: same-noise parity with the float64 reference under the bar rule of
+    test_same_noise_parity_with_the_float64_reference_at_size.  Generator: eks_sample(seed) equals
+    eks_sample(noise = eks_sample_noise(seed)) bit for bit (so the generator path shares the arithmetic held to the
+    tight bar above), its normals are ref.scalar_noise's within the 1e-4 the suite allows the hardware log2 / sin / cos,
+    and its draws are the reference's on ref.scalar_noise's normals within the parity bar plus what 1e-4 on every
+    normal can move a deviation: e is linear in z with non-negative coefficients (G_t >= 0 for a > 0), so that is
+    1e-4 e(z = 1), computed by the float64 reference.  A wrong lane, chain or counter word is an O(1) difference.
+    Measured on the MI355X, worst over the 90 shapes: kernels 9.1e-7 beyond the output rounding, transcription 9.5e-7
+    (bar 1e-5); ms 7.5e-7 (3.8e-7 over the shapes of 31 frames and more); generator max |dz| 3.4e-5."""
+    from eks_amd import hip_ops
+    S, N = 3, K * D
+    for unit in (True, False):
+        pb = make_chains(T, K, D, 2.0 if unit else 0.7, unit, seed=1000 * N + T)
+        Pf, ms64, Vs64, _ = ref_chain(pb)
+        sd = np.sqrt(Vs64)
+        # scale of a chain's means: its largest |ms|, the suite's scale.  With one to three frames that can itself be a
+        # cancelled value far below its operands (ms_0 = (1 - k c) m0 + k y: at K, D, T = 21, 3, 1 one chain has
+        # |ms| = 1.5e-3 from operands near one), where float32 arithmetic on those operands owes no relative accuracy;
+        # there, and only there, |m0| enters the scale: |k y| <= |ms_0| + |m0| bounds the operands by it.
+        scale = np.abs(ms64).max(axis=0)
+        if T <= 3:
+            scale = np.maximum(scale, np.abs(pb['m0f']))
+
+        def parity(dr, ms, z):
+            e64 = ref.scalar_deviations(Pf, pb['a'], pb['qs'], z)
+            e32 = ref.scalar_deviations_f32(pb['var'], pb['S0d'], pb['a'], pb['c'], pb['qs'], z)
+            trans = float(np.abs((e32 - e64) / sd).max())
+            trans_out = float(np.abs((ref.read_through_f32_output(ms64, e32) - e64) / sd).max())
+            return e64, max(1e-5, 4 * trans), max(1e-5, 4 * trans_out), trans, trans_out
+
+        # injected normals
+        z = np.random.default_rng(N + T).normal(size=(S, T, N)).astype(np.float32)
+        dr, ms = gpu_sample(pb, S, noise=z)
+        assert dr.shape == (S, T, N) and np.isfinite(dr).all()
+        e64, bar, bar_raw, trans, trans_out = parity(dr, ms, z)
+        err = dev_error(dr - ms[None], e64, dr, sd)
+        raw = float(np.abs((dr - ms[None] - e64) / sd).max())
+        print(f'edge K={K} D={D} T={T} unit={unit} injected: kernels {err:.3g} beyond the output rounding, float32 '
+              f'transcription {trans:.3g}, bar {bar:.3g}; raw {raw:.3g}, transcription through the float32 output '
+              f'{trans_out:.3g}, bar {bar_raw:.3g}; ms {(np.abs(ms - ms64) / scale).max():.3g} (relative to the '
+              f"chain's largest |ms| alone: {(np.abs(ms - ms64) / np.abs(ms64).max(axis=0)).max():.3g}), bar 1e-05")
+        assert err < bar
+        assert raw < bar_raw
+        assert (np.abs(ms - ms64) / scale).max() < 1e-5
+        # the generator
+        seed = 0x5eed0000 + 977 * N + T
+        gen, ms_g = gpu_sample(pb, S, seed=seed)
+        assert np.array_equal(ms_g, ms)
+        nz = hip_ops.sample_noise(T, K, D, D, S, seed=seed, flags=_flags(pb))
+        torch.cuda.synchronize()
+        nz = nz.cpu().numpy().reshape(S, T, N)
+        inj, _ = gpu_sample(pb, S, noise=nz)
+        assert np.array_equal(gen, inj)                                   # (T % 4 != 0 included)
+        zr = ref.scalar_noise(seed, T, N, S)
+        dz = float(np.abs(nz - zr).max())
+        e64, bar, bar_raw, trans, trans_out = parity(gen, ms_g, zr)
+        moved = 1e-4 * ref.scalar_deviations(Pf, pb['a'], pb['qs'], np.ones((1, T, N)))[0] / sd
+        excess = np.maximum(np.abs(gen - ms_g[None] - e64) - 2.0 ** -24 * np.abs(gen), 0.0) / sd - moved[None]
+        print(f'edge K={K} D={D} T={T} unit={unit} generator: max |dz| {dz:.3g} (bar 1e-04); error beyond the output '
+              f'rounding and 1e-4 per normal {max(float(excess.max()), 0.0):.3g}, bar {bar:.3g}')
+        assert dz < 1e-4
+        assert excess.max() < bar
 
 
 def test_generator_noise_tiling_over_keypoints_draws_and_memory_budget_are_bit_exact():
@@ -287,3 +355,52 @@ def test_sample_singlecam_on_the_golden_markers(golden_dir):
     got = stats(dr.reshape(S, T, K * 2).astype(np.float64) - mean_col[None])
     print(f'sample_singlecam: worst |stat| / se = {np.abs(got / se).max():.2f}')
     assert np.all(np.abs(got) < 6 * se)
+
+
+def test_sample_abi_refuses_what_it_documents_without_launching():
+    """Through the library, with real device buffers: every refusal below is returned by a guard that runs before the
+    first launch (eks_api.hip: eks_sample, eks_sample_noise; eks_sample_dense.hip: dense_sample checks D, O, then
+    (n_draws + 1) K D, then the workspace)."""
+    import ctypes
+    from eks_amd import _lib
+    lib = _lib.load()
+    f32 = torch.zeros(1 << 16, dtype=torch.float32, device='cuda')
+    f64 = torch.zeros(1 << 16, dtype=torch.float64, device='cuda')
+    ws = torch.zeros(1 << 22, dtype=torch.uint8, device='cuda')
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    par = [p(f64)] * 6
+
+    def sample(d, n_draws, draws, ws_bytes):
+        return lib.eks_sample(ctypes.byref(d), p(f32), p(f32), *par, n_draws, 0, 0, 0, None, None, draws, p(ws),
+                              ws_bytes, None)
+    diag = _lib.EksDims(4, 100, 2, 2, _lib.FLAG_DIAG_MODEL)                   # K, T, D, O, flags
+    gen = _lib.EksDims(4, 100, 3, 4, 0)
+    for d in (diag, gen):
+        need = lib.eks_sample_workspace_bytes(ctypes.byref(d), 2)
+        assert 0 < need <= ws.numel()
+        rc = sample(d, 2, p(f32), need - 1)                                   # one byte short
+        assert rc == -4 and b'workspace' in lib.eks_status_string(rc)
+        assert sample(d, 2, None, need) == -1                                 # null draws
+        assert sample(d, 0, p(f32), need) == -2                               # n_draws < 1
+    d7 = _lib.EksDims(4, 100, 7, 7, 0)
+    rc = sample(d7, 2, p(f32), ws.numel())
+    assert rc == -3 and b'unsupported' in lib.eks_status_string(rc)           # D = 7 on a general model
+    assert sample(_lib.EksDims(4, 100, 3, 65, 0), 2, p(f32), ws.numel()) == -3    # O = 65
+    # (n_draws + 1) K D = 8 x 2^20 x 3 > 2^24 (K D itself passes check_dims); the workspace named is too small for any
+    # launch of that shape as well
+    wide = _lib.EksDims(1 << 20, 4, 3, 4, 0)
+    assert lib.eks_smooth_workspace_bytes(ctypes.byref(wide)) > 0
+    rc = sample(wide, 7, p(f32), 16)
+    assert rc == -2 and b'shape' in lib.eks_status_string(rc)
+    assert sample(wide, 0x7fffffff, p(f32), 16) == -2                         # n_draws + 1 does not wrap
+    # eks_sample_workspace_bytes is 0 for what eks_sample refuses
+    for d, n in ((d7, 2), (_lib.EksDims(4, 100, 3, 65, 0), 2), (wide, 7), (wide, 0x7fffffff), (gen, 0), (diag, 0),
+                 (_lib.EksDims(4, 100, 2, 3, _lib.FLAG_DIAG_MODEL), 2), (_lib.EksDims(4, 0, 3, 4, 0), 2)):
+        assert lib.eks_sample_workspace_bytes(ctypes.byref(d), n) == 0
+    assert lib.eks_sample_workspace_bytes(ctypes.byref(wide), 4) > 0          # 5 x 2^20 x 3 <= 2^24 is accepted
+    # eks_sample_noise: W = D + O > 70 is a shape error; a refused model within 70 normals stays "unsupported"
+    assert lib.eks_sample_noise(ctypes.byref(_lib.EksDims(4, 100, 7, 64, 0)), 2, 0, 0, 0, p(f32), None) == -2
+    assert lib.eks_sample_noise(ctypes.byref(_lib.EksDims(4, 100, 3, 68, 0)), 2, 0, 0, 0, p(f32), None) == -2
+    assert lib.eks_sample_noise(ctypes.byref(d7), 2, 0, 0, 0, p(f32), None) == -3
+    assert lib.eks_sample_noise(ctypes.byref(gen), 2, 0, 0, 0, None, None) == -1
+    torch.cuda.synchronize()                                                  # nothing was enqueued, nothing faulted

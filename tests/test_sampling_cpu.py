@@ -187,6 +187,92 @@ def test_exact_law_on_a_short_session_through_the_lane_code(sim):
     assert worst < bar
 
 
+def dense_model(K, D, O, seed):
+    rng = np.random.default_rng(seed)
+    A = np.eye(D) * 0.95 + 0.05 * rng.normal(size=(K, D, D)) / np.sqrt(D)
+    C = rng.normal(size=(K, O, D))
+    Lq = rng.normal(size=(K, D, D)) * 0.4 + np.eye(D)
+    Q = Lq @ np.swapaxes(Lq, 1, 2)                                   # non-diagonal, positive definite
+    L0 = rng.normal(size=(K, D, D)) * 0.3 + 1.5 * np.eye(D)
+    S0 = L0 @ np.swapaxes(L0, 1, 2)
+    return dict(m0=rng.normal(size=(K, D)), S0=S0, A=A, C=C, Q=Q, s=rng.uniform(0.5, 2.0, K))
+
+
+def drop_one_direction(M, names, seed):
+    """M with one random eigen-direction per keypoint projected out of the matrices `names` (rank D - 1, exactly
+    symmetric); D = 1 leaves a zero."""
+    rng = np.random.default_rng(seed)
+    M = dict(M)
+    for nm in names:
+        K, D, _ = M[nm].shape
+        u = rng.normal(size=(K, D))
+        u /= np.linalg.norm(u, axis=1, keepdims=True)
+        Pj = np.eye(D) - u[:, :, None] * u[:, None, :]
+        X = Pj @ M[nm] @ Pj
+        M[nm] = 0.5 * (X + np.swapaxes(X, 1, 2))
+    return M
+
+
+def short_dense_session(T, K, O, seed=1):
+    rng = np.random.default_rng(seed)
+    var = np.exp(rng.normal(0.0, 0.7, (T, K, O))).astype(np.float32)
+    var[5, 1, min(2, O - 1)] = 1000.0
+    return rng.normal(size=(T, K, O)).astype(np.float32), var
+
+
+def dense_law_error(dev, var, M):
+    """dev [1 + T W][T][K][D] from unit_noise: worst law_error over the keypoints against dense_joint_posterior."""
+    T, K, D = dev.shape[1:]
+    worst = 0.0
+    for k in range(K):
+        S = ref.dense_joint_posterior(var[:, k], M['S0'][k], M['A'][k], M['C'][k], M['Q'][k], M['s'][k])
+        worst = max(worst, ref.law_error(dev[1:, :, k].reshape(-1, T * D).T.astype(np.float64), S))
+    return worst
+
+
+@pytest.mark.parametrize('singular', [(), ('Q',), ('S0',), ('Q', 'S0')])
+@pytest.mark.parametrize('D,O', [(1, 3), (3, 4), (6, 12)])
+def test_dense_durbin_koopman_reference_has_the_exact_law(D, O, singular):
+    """ref.dense_durbin_koopman in float64 against the joint posterior covariance by plain linear algebra: the
+    deviations of the T (D + O) unit normals are the columns of a factor of it.  Plain float64 gives 4.6e-14 at
+    D, O = 1, 3, 2.8e-13 at 3, 4 and 4.8e-13 at 6, 12 (the worst over full-rank and rank D - 1 Q / S0); the bar is
+    a decade above the worst of these.  At D = 1 a rank-deficient S0 is zero and leaves frame 0 without variance to
+    normalise by, so that case keeps S0 and drops Q alone."""
+    T, K = 12, 3
+    if D == 1:
+        singular = tuple(n for n in singular if n != 'S0')
+    M = drop_one_direction(dense_model(K, D, O, seed=D), singular, seed=7)
+    for nm in singular:
+        assert np.linalg.matrix_rank(M[nm][0]) == D - 1
+    y, var = short_dense_session(T, K, O)
+    z = unit_noise(T, K, D + O)
+    ms, Vs, dev = ref.dense_durbin_koopman(y, var, M['m0'], M['S0'], M['A'], M['C'], M['Q'], M['s'], z)
+    assert dev.shape == (z.shape[0], T, K, D) and ms.shape == (T, K, D) and Vs.shape == (T, K, D, D)
+    assert np.abs(dev[0]).max() == 0.0                                   # z = 0 returns the smoothed mean
+    worst, bar = dense_law_error(dev, var, M), 5e-12
+    print(f'law, float64 Durbin-Koopman reference D={D} O={O} singular={singular}: {worst:.3g}, bar {bar:.3g}')
+    assert worst < bar
+    for k in range(K):                                                   # its Vs are that covariance's diagonal blocks
+        S = ref.dense_joint_posterior(var[:, k], M['S0'][k], M['A'][k], M['C'][k], M['Q'][k], M['s'][k])
+        for t in range(T):
+            blk = S[t * D:(t + 1) * D, t * D:(t + 1) * D]
+            assert np.abs(Vs[t, k] - blk).max() < 1e-10 * np.abs(blk).max()
+    # the float32-storage transcription differs by float32 rounding of O(|x+|), no more
+    _, _, dev32 = ref.dense_durbin_koopman(y, var, M['m0'], M['S0'], M['A'], M['C'], M['Q'], M['s'], z,
+                                           storage=np.float32)
+    sd = np.sqrt(np.diagonal(Vs, axis1=-2, axis2=-1))
+    assert 0.0 < np.abs((dev32 - dev) / sd).max() < 1e-5
+
+
+def test_chol_psd_zero_pivot_rule():
+    M = np.array([[[4.0, 2.0, 0.0], [2.0, 1.0, 0.0], [0.0, 0.0, 9.0]],          # second pivot exactly zero
+                  [[0.0, 0.0, 0.0], [0.0, 2.0, 1.0], [0.0, 1.0, 5.0]]])         # first pivot zero
+    L = ref.chol_psd(M)
+    assert np.array_equal(L[0], [[2.0, 0, 0], [1.0, 0, 0], [0, 0, 3.0]])
+    assert np.all(L[1][:, 0] == 0) and np.abs(L[1] @ L[1].T - M[1]).max() < 1e-15
+    assert np.all(np.triu(L, 1) == 0)
+
+
 def test_draws_do_not_depend_on_tiling_over_keypoints_or_draws(sim):
     pb = make_chains(70, 4, 2, 2.0, True, seed=3)
     _, full = run_sim(sim, pb, 16, 6, seed=99)
@@ -230,6 +316,16 @@ def test_sampling_entry_points_are_declared_bound_and_exported(lib):
     assert lib.eks_sample(ctypes.byref(d), *args, 1, 0, 0, 0, None, None, one, one, 16, None) == -4
     big = _lib.EksDims(4, 100, 7, 7, 0)
     assert lib.eks_sample(ctypes.byref(big), *args, 1, 0, 0, 0, None, None, one, one, 1 << 40, None) == -3
+    need = lib.eks_sample_workspace_bytes(ctypes.byref(g), 2)
+    assert lib.eks_sample(ctypes.byref(g), *args, 2, 0, 0, 0, None, None, one, one, need - 1, None) == -4   # a byte short
+    # (n_draws + 1) K D > 2^24 stacked chains on a general model: a shape error, and no workspace size
+    wide = _lib.EksDims(1 << 20, 4, 3, 4, 0)
+    assert lib.eks_sample(ctypes.byref(wide), *args, 7, 0, 0, 0, None, None, one, one, 1 << 40, None) == -2
+    assert lib.eks_sample_workspace_bytes(ctypes.byref(wide), 7) == 0
+    assert lib.eks_sample_workspace_bytes(ctypes.byref(wide), 4) > 0
+    assert lib.eks_sample_workspace_bytes(ctypes.byref(big), 1) == 0
+    assert lib.eks_sample_noise(ctypes.byref(_lib.EksDims(4, 100, 7, 64, 0)), 1, 0, 0, 0, one, None) == -2   # W = 71
+    assert lib.eks_sample_noise(ctypes.byref(big), 1, 0, 0, 0, one, None) == -3
     assert lib.eks_sample_noise(ctypes.byref(d), 0, 0, 0, 0, one, None) == -2
     assert lib.eks_sample_noise(ctypes.byref(d), 1, 0, 0, 0, None, None) == -1
 
@@ -280,3 +376,37 @@ def test_draw_groups_follow_the_memory_budget(lib):
     g = draws_per_group(64, 20000, 2, 2, fl, 16, 50 << 20)
     assert 1 <= g < 16
     assert draws_per_group(64, 20000, 2, 2, fl, 16, 1) == 1
+
+
+@pytest.mark.parametrize('D,O', [(1, 3), (3, 4), (6, 12)])
+def test_reference_filter_by_scalar_updates_against_both_formulations_of_the_oracle(D, O):
+    """ref.filter_by_scalar_updates (+ the oracle's RTS pass), the smoother inside dense_durbin_koopman, against
+    oracle.eks_oracle.kalman_smoother (joint update through inv(S)) on 300 frames with variances within four decades,
+    and against the oracle's information-form smoother after one variance of the first and of the last keypoint is
+    set to the 1e30 clip, where inv(S) is not to be trusted.  Plain float64 gives at most 3.8e-13 (Vs, D, O = 6, 12)
+    and 1.9e-14; the bar is 5e-12, a decade above the larger."""
+    from oracle import eks_oracle as orc
+    T, K = 300, 3
+    M = dense_model(K, D, O, seed=D)
+    rng = np.random.default_rng(5)
+    R = np.exp(rng.normal(0, 0.7, (K, T, O)))
+    R[:, ::17] = 1000.0
+    y = rng.normal(size=(K, T, O))
+    par = tuple(M[k] for k in ('m0', 'S0', 'A', 'C', 'Q', 's'))
+
+    def worst(a, Va, b, Vb):
+        return max(float((np.abs(a - b) / np.abs(a).max(axis=1, keepdims=True)).max()),
+                   float((np.abs(Va - Vb) / np.abs(Va).max(axis=1, keepdims=True)).max()))
+    figures = []
+    for spread in (False, True):
+        if spread:
+            R[0, T // 3, 0] = R[K - 1, (2 * T) // 3, O - 1] = ref.VAR_CEIL
+            a, Va = orc.info_form_smoother(y, *par, R)[:2]
+        else:
+            a, Va = orc.kalman_smoother(y, *par, R)[:2]
+        mf, Pf = ref.filter_by_scalar_updates(y, *par, R)
+        b, Vb = orc.rts_smoother(mf, Pf, M['A'], M['Q'], M['s'])
+        figures.append(worst(a, Va, b, Vb))
+    print(f'scalar-update filter D={D} O={O}: against kalman_smoother {figures[0]:.3g}, with a variance at 1e30 against '
+          f'the information form {figures[1]:.3g}, bar 5e-12')
+    assert max(figures) < 5e-12
