@@ -20,6 +20,7 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'run_kalman_smoother': 'core', 'ensemble': 'core', 'optimize_smooth_param': 'core',
         'DifferentiableEmission': 'emission',
         'sample_kalman_posterior': 'posterior', 'sample_singlecam': 'posterior',
+        'smooth_increments': 'posterior', 'velocity_singlecam': 'posterior',
     }
     if name in table:
         return getattr(importlib.import_module(f'.{table[name]}', __name__), name)

@@ -32,6 +32,8 @@ SIGNATURES = {
     'eks_status_string': (c_char_p, [ctypes.c_int]),
     'eks_smooth_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
     'eks_smooth': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
+    'eks_smooth_increments_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
+    'eks_smooth_increments': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 14 + [c_size_t, c_void_p]),
     'eks_sample_noise_width': (c_int32, [POINTER(EksDims)]),
     'eks_sample_workspace_bytes': (c_size_t, [POINTER(EksDims), c_int32]),
     'eks_sample': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 8 + [c_int32, ctypes.c_uint64, c_int32, c_int32]

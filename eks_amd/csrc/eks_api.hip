@@ -62,6 +62,43 @@ int eks_smooth(const eks_dims_t* d, const float* y, const float* var, const doub
   return dense_smooth(*d, y, var, M, ms, Vs, workspace, workspace_bytes, st);
 }
 
+// shapes eks_smooth_increments takes (EKS_OK) or the status it refuses them with; nothing here touches the device
+static int increments_check(const eks_dims_t* d) {
+  const int rc = check_dims(d);
+  if (rc != EKS_OK) return rc;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) {
+    if (!(d->flags & EKS_FLAG_VS_DIAG)) return EKS_ERR_UNSUPPORTED;   // off-diagonals are identically zero
+    return diag_increments_covers(d->n_frames, d->n_keypoints * d->state_dim) ? EKS_OK : EKS_ERR_SHAPE;
+  }
+  if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
+  return EKS_OK;
+}
+
+size_t eks_smooth_increments_workspace_bytes(const eks_dims_t* d) {
+  if (increments_check(d) != EKS_OK) return 0;
+  if (d->flags & EKS_FLAG_DIAG_MODEL)
+    return diag_increments_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
+  return dense_increments_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+}
+
+int eks_smooth_increments(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
+                          const double* A, const double* C, const double* Q, const double* s, float* ms, float* Vs,
+                          float* lag1, float* dmean, float* dV, void* workspace, size_t workspace_bytes,
+                          eks_stream_t stream) {
+  const int rc = increments_check(d);
+  if (rc != EKS_OK) return rc;
+  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s) return EKS_ERR_NULL;
+  if (!lag1 && !dmean && !dV) return EKS_ERR_NULL;
+  if (!workspace) return EKS_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (d->flags & EKS_FLAG_DIAG_MODEL) {
+    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
+    return diag_increments(*d, y, var, M, ms, Vs, lag1, dmean, dV, workspace, workspace_bytes, st);
+  }
+  const DenseModel M{m0, S0, A, C, Q, s};
+  return dense_increments(*d, y, var, M, ms, Vs, lag1, dmean, dV, workspace, workspace_bytes, st);
+}
+
 int32_t eks_sample_noise_width(const eks_dims_t* d) {
   if (check_dims(d) != EKS_OK) return 0;
   return (d->flags & EKS_FLAG_DIAG_MODEL) ? d->state_dim : d->state_dim + d->obs_dim;

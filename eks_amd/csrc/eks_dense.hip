@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "eks_dense_lane.hpp"
+#include "eks_increments_lane.hpp"
 #include "eks_internal.hpp"
 
 namespace eks {
@@ -407,6 +408,96 @@ int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const De
                            dim3(64), 0, st, G, M, Mm.s, obs, pre, suf, bprior, bsuffix, filt, ms, Vs,
                            vs_diag, nullptr, nullptr, nullptr, open);
       }
+    }
+  })
+  return hip_status(hipGetLastError());
+}
+
+// ---- eks_smooth_increments on general models: a third mode of the generic organisation ---------------------
+// dense_summarize -> dense_scan -> dense_scan_blocks as they are, then a replay that also emits lag1, dmean and dV
+// (eks_increments_lane.hpp: dense_increments_chunk).  Always the generic kernels and their workspace layout, whatever
+// dense_path would pick for eks_smooth: correct first, like the dense sampler.
+template <int D, typename Obs>
+__global__ __launch_bounds__(64) void dense_increments_kernel(DenseGeom G, DenseModelPtrs M,
+                                                             const double* __restrict__ s, Obs obs,
+                                                             const double* __restrict__ pre,
+                                                             const double* __restrict__ suf,
+                                                             const double* __restrict__ bprior,
+                                                             const double* __restrict__ bsuffix,
+                                                             double* __restrict__ filt, DenseIncrementsOut out) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.nc) return;
+  constexpr int REC = D + D * D;
+  constexpr int NV = delem_doubles<D>();
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  Vec<double, D> m, eta;
+  Mat<double, D> P, J;
+  // one element per lane (Bs == B): boundaries as in dense_replay_kernel
+  const int blk = j / kDenseCB, ia = j % kDenseCB;
+  const double* rp = bprior + ((size_t)blk * G.K + k) * REC;
+  const double* rs = bsuffix + ((size_t)blk * G.K + k) * REC;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    m.a[a] = rp[a];
+    eta.a[a] = rs[a];
+#pragma unroll
+    for (int b = 0; b < D; ++b) {
+      P.a[a][b] = rp[D + a * D + b];
+      J.a[a][b] = rs[D + a * D + b];
+    }
+  }
+  if (ia > 0) delem_apply(load_delem<double, D>(pre + ((size_t)(j - 1) * G.K + k) * NV), m, P);
+  if (ia + 1 < kDenseCB && j + 1 < G.nc)
+    delem_back(load_delem<double, D>(suf + ((size_t)(j + 1) * G.K + k) * NV), eta, J);
+  if (j == 0) load_prior<D>(M, k, m, P);   // chunk 0 replays frame 0's update of the prior itself
+  const int t0 = j * G.B, len = min(G.B, G.T - t0);
+  dense_increments_chunk<D, Obs>(obs, G.K, k, t0, len, F, sQ, fid, m, P, eta, J, filt + (size_t)t0 * REC * G.K + k, out,
+                                 (size_t)G.K);
+}
+
+size_t dense_increments_workspace_bytes(int T, int K, int D, int O) {
+  if (D < 1 || D > 6 || O < 1 || O > 64) return 0;
+  const int B = dense_chunk(T, K), nc = (T + B - 1) / B;
+  if ((long long)K * nc >= (1 << 30)) return 0;   // dense_increments: EKS_ERR_SHAPE
+  return generic_layout(T, K, D, nc, nullptr).bytes;
+}
+
+int dense_increments(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, float* ms, float* Vs,
+                     float* lag1, float* dmean, float* dV, void* ws, size_t ws_bytes, hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
+  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
+  DenseGeom G{K, T, O, dense_chunk(T, K), 0, 0, 0};
+  G.nc = (T + G.B - 1) / G.B;
+  G.Bs = G.B;
+  G.ncs = G.nc;
+  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
+  if (ws_bytes < dense_increments_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
+  const int nblk = (G.nc + kDenseCB - 1) / kDenseCB, lanes = K * G.nc;
+  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
+  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
+  const DenseIncrementsOut out{ms, Vs, lag1, dmean, dV, (d.flags & EKS_FLAG_VS_DIAG) != 0, T};
+  const Gate open{nullptr, 0.0};
+  EKS_DISPATCH_D(D, {
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
+    {
+      ProfScope ps("dense_increments_summarize", st);
+      hipLaunchKernelGGL((dense_summarize_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
+                         Mm.s, obs, L.elems, L.first, open);
+    }
+    {
+      ProfScope ps("dense_increments_scan", st);
+      hipLaunchKernelGGL(dense_scan_kernel<DD>, dim3(K, nblk), dim3(2 * kDenseCB), 0, st, G, L.elems, L.pre, L.suf,
+                         L.agg, open);
+      hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk, L.first, L.agg,
+                         L.bprior, L.bsuffix, open);
+    }
+    {
+      ProfScope ps("dense_increments_replay", st);
+      hipLaunchKernelGGL((dense_increments_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
+                         Mm.s, obs, L.pre, L.suf, L.bprior, L.bsuffix, L.filt, out);
     }
   })
   return hip_status(hipGetLastError());

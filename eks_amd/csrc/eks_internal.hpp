@@ -116,6 +116,15 @@ int dense_sample_noise(int T, int K, int W, int n_draws, uint64_t seed, int firs
 struct DenseModel {
   const double *m0, *S0, *A, *C, *Q, *s;
 };
+// eks_smooth plus lag-one covariances and the posterior of increments (eks_increments.hip: scalar chains;
+// eks_dense.hip: general models, always the generic kernels)
+bool diag_increments_covers(int T, int N);
+size_t diag_increments_workspace_bytes(int T, int N);
+int diag_increments(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, float* ms, float* Vs,
+                    float* lag1, float* dmean, float* dV, void* ws, size_t ws_bytes, hipStream_t st);
+size_t dense_increments_workspace_bytes(int T, int K, int D, int O);
+int dense_increments(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, float* ms, float* Vs,
+                     float* lag1, float* dmean, float* dV, void* ws, size_t ws_bytes, hipStream_t st);
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M,
                  float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);

@@ -200,6 +200,40 @@ def smooth(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False, ou
     return PreparedSmooth(y, var, m0, S0, A, C, Q, s, flags, vs_diag, out)()
 
 
+def smooth_increments(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False,
+                      want=('lag1', 'dmean', 'dV'), want_smooth: bool = True):
+    """eks_smooth_increments: eks_smooth plus lag1 = Cov(x_t, x_{t+1} | y), dmean = E[x_{t+1} - x_t | y] and
+    dV = Cov(x_{t+1} - x_t | y), every array with T rows (row T-1 of the three is zero).  Returns a dict of device
+    tensors: ms (T, K, D) and Vs (unless want_smooth is False) and the outputs named in `want`; Vs, lag1, dV are
+    (T, K, D) diagonals with vs_diag, (T, K, D, D) without.  Scalar chains (FLAG_DIAG_MODEL) exist with vs_diag only."""
+    lib = _lib.load()
+    T, K, O = y.shape
+    D = m0.shape[-1]
+    want = tuple(want)
+    if not want or any(w not in ('lag1', 'dmean', 'dV') for w in want):
+        raise ValueError("want must name at least one of 'lag1', 'dmean', 'dV'")
+    y = _chk(y, torch.float32, 'y')
+    var = _chk(var, torch.float32, 'var', (T, K, O))
+    m0 = _chk(m0, torch.float64, 'm0', (K, D))
+    S0 = _chk(S0, torch.float64, 'S0', (K, D, D))
+    A = _chk(A, torch.float64, 'A', (K, D, D))
+    C = _chk(C, torch.float64, 'C', (K, O, D))
+    Q = _chk(Q, torch.float64, 'Q', (K, D, D))
+    s = _chk(s, torch.float64, 's', (K,))
+    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
+    dims = _dims(K, T, D, O, flags)
+    cov = (T, K, D) if vs_diag else (T, K, D, D)
+    shapes = dict(ms=(T, K, D), Vs=cov, lag1=cov, dmean=(T, K, D), dV=cov)
+    names = (('ms', 'Vs') if want_smooth else ()) + want
+    out = {n: torch.empty(shapes[n], dtype=torch.float32, device=y.device) for n in shapes if n in names}
+    ws = _workspace(lib.eks_smooth_increments_workspace_bytes(ctypes.byref(dims)), y.device)
+    rc = lib.eks_smooth_increments(ctypes.byref(dims), _ptr(y), _ptr(var), _ptr(m0), _ptr(S0), _ptr(A), _ptr(C), _ptr(Q),
+                                   _ptr(s), *(_ptr(out.get(n)) for n in ('ms', 'Vs', 'lag1', 'dmean', 'dV')), _ptr(ws),
+                                   ws.numel(), _stream())
+    _lib.check(rc, 'eks_smooth_increments')
+    return out
+
+
 def sample_noise_width(D: int, O: int, flags: int) -> int:
     """eks_sample_noise_width: standard normals consumed per (draw, frame, keypoint)."""
     return int(_lib.load().eks_sample_noise_width(ctypes.byref(_dims(1, 1, D, O, flags))))

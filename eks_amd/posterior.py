@@ -7,17 +7,24 @@ white-noise paths.  The reference has no counterpart.
 
     sample_kalman_posterior(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, n_draws, ...) -> (K, n_draws, T, D)
     sample_singlecam(marker_array, keypoint_names, s_finals, n_draws, ...) -> (n_draws, T, K, 2) in pixels
+
+The commonest such quantity - the frame-to-frame increment x_{t+1} - x_t behind velocity, speed and movement onsets -
+has a closed form inside the smoother's backward pass and needs no draws:
+
+    smooth_increments(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, ...) -> (ms, Vs, lag1, dmean, dV)
+    velocity_singlecam(marker_array, keypoint_names, s_finals, fps=...) -> velocity, velocity_var, speed_rms
 """
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from typing import Literal
 
 import numpy as np
 
 from . import hip_ops
 
-__all__ = ['sample_kalman_posterior', 'sample_singlecam']
+__all__ = ['sample_kalman_posterior', 'sample_singlecam', 'smooth_increments', 'velocity_singlecam', 'SmoothIncrements']
 
 DEFAULT_MEMORY_BUDGET = 2 << 30     # bytes of device memory one group of draws (output + workspace) may take
 
@@ -136,3 +143,75 @@ def sample_singlecam(marker_array, keypoint_names: list, s_finals, n_draws: int,
                                     seed=seed, memory_budget=memory_budget)
     mu = np.asarray(means.array)[0, 0, 0].astype(np.float32)                     # (K,2)
     return np.ascontiguousarray(np.transpose(draws, (1, 2, 0, 3))) + mu[None, None]
+
+
+SmoothIncrements = namedtuple('SmoothIncrements', ['ms', 'Vs', 'lag1', 'dmean', 'dV'])
+
+
+def smooth_increments(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, full_cov: bool = False,
+                      return_device: bool = False, h_fn=None) -> SmoothIncrements:
+    """The smoother's marginals plus the posterior of the frame-to-frame increment, at the smoothing parameters
+    s_finals (scalar or (K,)), in one pass.  Arguments as sample_kalman_posterior.  Returns the named tuple
+        ms (K, T, D), Vs, lag1 = Cov(x_t, x_{t+1} | y), dmean (K, T-1, D) = E[x_{t+1} - x_t | y],
+        dV = Cov(x_{t+1} - x_t | y)
+    with Vs (K, T, D) and lag1, dV (K, T-1, D) holding diagonals, or the D x D matrices with full_cov (lag1: row =
+    coordinate of x_t, column = coordinate of x_{t+1}).  float32 NumPy arrays, or device tensors with return_device;
+    all are views of the kernels' frame-major buffers, like run_kalman_smoother's.  dV is formed inside the
+    backward pass as a sum of non-negative terms: Vs[t] + Vs[t+1] - 2 lag1[t] from the float32 outputs loses it to
+    cancellation under heavy smoothing."""
+    K, T, O, D, s = _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, 1, h_fn, 0, 0)
+    flags = _host_flags(S0s, As, Cs, Qs)
+    from . import _lib
+    from .core import _DeviceProblem, _to_host, _torch
+    torch = _torch()
+    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
+    diag_model = bool(P.flags & _lib.FLAG_DIAG_MODEL)
+    out = hip_ops.smooth_increments(P.y, P.var, *P.params, torch.as_tensor(s, device=P.dev), flags=P.flags,
+                                    vs_diag=diag_model or not full_cov)
+    names = SmoothIncrements._fields
+    if return_device:
+        res = {n: out[n] for n in names}
+        if diag_model and full_cov:                     # scalar chains: the matrices are the diagonal embedding
+            res.update({n: torch.diag_embed(res[n]) for n in ('Vs', 'lag1', 'dV')})
+        swap = lambda a: a.transpose(0, 1)
+    else:
+        res = dict(zip(names, _to_host(*(out[n] for n in names))))
+        if diag_model and full_cov:
+            eye = np.eye(D, dtype=np.float32)
+            res.update({n: res[n][..., :, None] * eye for n in ('Vs', 'lag1', 'dV')})
+        swap = lambda a: np.swapaxes(a, 0, 1)
+    return SmoothIncrements(swap(res['ms']), swap(res['Vs']), swap(res['lag1'])[:, :T - 1], swap(res['dmean'])[:, :T - 1],
+                            swap(res['dV'])[:, :T - 1])
+
+
+def velocity_singlecam(marker_array, keypoint_names: list, s_finals, *, fps: float = 1.0,
+                       avg_mode: Literal['mean', 'median'] = 'median',
+                       var_mode: Literal['var', 'confidence_weighted_var'] = 'confidence_weighted_var') -> dict:
+    """Posterior of the velocity of the single-camera smoother, in pixels per second at `fps` frames per second.
+    Rebuilds the ensemble, the centring and the prior as ensemble_kalman_smoother_singlecam does (the centring means
+    cancel in an increment, so nothing is added back).  Returns a dict of float32 arrays:
+        velocity     (T-1, K, 2)  E[x_{t+1} - x_t | y] fps
+        velocity_var (T-1, K, 2)  Var(x_{t+1} - x_t | y) fps^2
+        speed_rms    (T-1, K)     sqrt(E |v|^2) = fps sqrt(sum_d dmean^2 + dV): the exact root of the second moment
+    s_finals: the smoothing parameters the driver returned."""
+    from .core import ensemble
+    from .singlecam_smoother import initialize_kalman_filter
+    from .utils import center_predictions
+    M, V, T, K, _ = marker_array.shape
+    if V != 1:
+        raise ValueError('velocity_singlecam takes a single-view marker array')
+    if len(keypoint_names) != K:
+        raise ValueError(f'{len(keypoint_names)} keypoint names for {K} keypoints')
+    if not fps > 0:
+        raise ValueError('fps must be positive')
+    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)
+    _, centered, _, _ = center_predictions(ens, quantile_keep_pca=100)
+    stats = np.asarray(ens.array)[0, 0]
+    cen = np.asarray(centered.array)[0, 0]
+    m0s, S0s, As, Qs, Cs = initialize_kalman_filter(centered)
+    inc = smooth_increments(np.swapaxes(cen, 0, 1), m0s, S0s, As, Cs, Qs, stats[:, :, 2:4], s_finals)
+    f = np.float32(fps)
+    dmean = np.swapaxes(inc.dmean, 0, 1)                                        # (T-1, K, 2)
+    dV = np.swapaxes(inc.dV, 0, 1)
+    return dict(velocity=dmean * f, velocity_var=dV * (f * f),
+                speed_rms=f * np.sqrt((dmean * dmean + dV).sum(axis=-1)))

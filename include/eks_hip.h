@@ -113,6 +113,32 @@ int eks_sample(const eks_dims_t* dims, const float* y, const float* var, const d
 int eks_sample_noise(const eks_dims_t* dims, int32_t n_draws, uint64_t seed, int32_t first_keypoint,
                      int32_t first_draw, float* noise, eks_stream_t stream);
 
+/* ---- eks_smooth plus the posterior of frame-to-frame increments.  No reference counterpart: the variance of
+ * x_{t+1} - x_t (velocity, speed, movement onsets) is not a function of the marginals ms, Vs; it needs
+ * Cov(x_t, x_{t+1} | y), which the RTS step holds in closed form.  dims, flags, inputs and the ms / Vs layouts are
+ * exactly those of eks_smooth (here ms and Vs may each be NULL).  For t = 0 .. T-2, with (mf, Pf) the filtered and
+ * (m', P') the smoothed belief of frame t+1, Pp the predicted covariance and G the smoother gain of frame t:
+ *   lag1[t]  = Cov(x_t, x_{t+1} | y) = G P'              row: coordinate of x_t, column: coordinate of x_{t+1}
+ *   dmean[t] = E[x_{t+1} - x_t | y]                       formed in the lane, not as a difference of float32 means
+ *   dV[t]    = Cov(x_{t+1} - x_t | y) = (I - G) P' (I - G)^T + (Pf - G Pp G^T)
+ * (scalar chains: G = a Pf / Pp, g = 1 - G: lag1 = G P', dmean = g (m' - a mf) - (1 - a) mf, dV = g^2 P' + Pf s q / Pp;
+ * a sum of non-negative products where Vs[t] + Vs[t+1] - 2 lag1[t] cancels).  Row T-1 of all three is zero.
+ *   dmean float32 [T][K][D]; lag1, dV follow the layout rule of Vs: [T][K][D] (diagonals) with EKS_FLAG_VS_DIAG,
+ *   [T][K][D][D] without.  Any of the three may be NULL, not all (EKS_ERR_NULL); a NULL output costs no stores.
+ *   scalar chains (EKS_FLAG_DIAG_MODEL): off-diagonals are identically zero, so the call exists with EKS_FLAG_VS_DIAG
+ *     only (EKS_ERR_UNSUPPORTED without); summarize, grouped Kalman scan, replay (eks_amd/csrc/eks_increments.hip):
+ *     y and var are read twice, every output is written once;
+ *   general models: D <= 6 and O <= 64 (else EKS_ERR_UNSUPPORTED); always the generic kernels of eks_smooth with a
+ *     replay that works in float64 and rounds once (eks_amd/csrc/eks_dense.hip: dense_increments); only Pp is
+ *     factored, so a singular Q or S0 is fine.
+ * A shape whose launches would index threads beyond an int is EKS_ERR_SHAPE.  Every refusal is returned before
+ * anything is enqueued, and the workspace query returns 0 for refused shapes. ------------------------------------ */
+size_t eks_smooth_increments_workspace_bytes(const eks_dims_t* dims);
+int eks_smooth_increments(const eks_dims_t* dims, const float* y, const float* var, const double* m0,
+                          const double* S0, const double* A, const double* C, const double* Q, const double* s,
+                          float* ms, float* Vs, float* lag1, float* dmean, float* dV, void* workspace,
+                          size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- constant observation noise for the loss: eks/core.py:702-709
  * rconst[k][o] = max(nanmedian_t max(var[t][k][o], 1e-12), min_var)  (float64 out) ----------- */
 size_t eks_const_r_workspace_bytes(const eks_dims_t* dims);
