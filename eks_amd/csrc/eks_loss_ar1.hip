@@ -21,8 +21,9 @@ int ar1_nll(const eks_dims_t& d, const float* y, const float* var, const double*
   if (ws_bytes < ar1_nll_workspace_bytes(T, K, D, n_tan)) return EKS_ERR_WORKSPACE;
   // Process noise positive in every coordinate (the caller's word: EKS_FLAG_Q_PD) on the pupil's shape: loss from
   // the exact filter inside the smoother's wave kernels, the tangents' derivatives from the smoothing distribution
-  // (eks_dense_wave.hip, MODE 2) instead of dual-number elements.
-  if (n_tan > 0 && (d.flags & EKS_FLAG_Q_PD) && dense_wave_ar1_covers(T, K, D, O))
+  // (eks_dense_wave.hip, MODE 2) instead of dual-number elements.  Its finishing launch gives one thread to a tangent
+  // (64 at most): more tangents than that take the dual-number form below, as they do without the flag.
+  if (n_tan > 0 && n_tan <= 64 && (d.flags & EKS_FLAG_Q_PD) && dense_wave_ar1_covers(T, K, D, O))
     return dense_wave_ar1_score(d, y, var, m0, S0, C, a, q, da, dq, n_tan, nll, dnll, ws, ws_bytes, st);
   const int ns = n_tan > 0 ? n_tan : 1;
   if ((long)K * ns > 65535) return EKS_ERR_UNSUPPORTED;

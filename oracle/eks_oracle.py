@@ -58,6 +58,17 @@ def _T(M):
     return np.swapaxes(M, -1, -2)
 
 
+def _quad_through(e, Sinv, dS):
+    """e' Sinv dS Sinv e per keypoint.  Up to 16 observations as ONE contraction (the order of operations the
+    committed vectors were made with); above, where that contraction's O^4 terms per frame take minutes per
+    session, the two vectors first."""
+    if e.shape[-1] <= 16:
+        return np.einsum('ko,kop,kpq,kqr,kr->k', e, Sinv, dS, Sinv, e)
+    left = np.einsum('ko,kop->kp', e, Sinv)
+    right = np.einsum('kqr,kr->kq', Sinv, e)
+    return np.einsum('kp,kpq,kq->k', left, dS, right)
+
+
 def _as_R_getter(R, K, T, O):
     """R may be (K,T,O) time-varying diagonal, (K,O) constant diagonal, or full matrices
     (K,T,O,O) / (K,O,O).  Returns f(t) -> (K,O,O)."""
@@ -143,7 +154,7 @@ def kalman_filter(y, m0, S0, A, C, Q, s, R, *, jitter=0.0, symmetrize=True, want
             de = -np.einsum('kod,kd->ko', C, dm)
             dll += -0.5 * (np.einsum('kop,kpo->k', Sinv, dS)
                            + 2.0 * np.einsum('ko,kop,kp->k', e, Sinv, de)
-                           - np.einsum('ko,kop,kpq,kqr,kr->k', e, Sinv, dS, Sinv, e))
+                           - _quad_through(e, Sinv, dS))
             dKg = np.matmul(np.matmul(dP, Ct), Sj_inv) - _bmm(Kg, dS, Sj_inv)
             dm = dm + np.einsum('kdo,ko->kd', dKg, e) + np.einsum('kdo,ko->kd', Kg, de)
             dP = dP - _bmm(dKg, S, _T(Kg)) - _bmm(Kg, dS, _T(Kg)) - _bmm(Kg, S, _T(dKg))

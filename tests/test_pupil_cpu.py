@@ -6,10 +6,12 @@
 * lane arithmetic: the dual-number AR(1) loss of the gfx950 kernels, compiled for the host from the
   same headers (tests/host_sim/dense_sim.cpp), against the oracle.
 * host logic: per-frame geometry, the checks of the reference's tests/test_ibl_pupil_smoother.py.
+* the reference helpers of tests/test_gpu_pupil_forms.py (basis combination, C against NumPy route, trajectory).
 """
 import ctypes
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -18,6 +20,8 @@ from oracle import c_oracle
 from oracle import eks_oracle as orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import test_gpu_pupil_forms as forms  # noqa: E402
 
 
 def synth_pupil(T, seed):
@@ -275,3 +279,93 @@ def test_fixed_parameters_bypass_and_no_gpu_refusal():
         ys, ev, m0, S0, lv = synth_pupil(20, seed=8)
         with pytest.raises(_lib.EksHipError):
             ips.run_pupil_kalman_smoother(ys, m0, S0, orc.PUPIL_C, ev, *lv, smooth_params=[0.9, 0.9])
+
+
+# ---------------------------------------------------------------------------------------------
+# reference helpers of tests/test_gpu_pupil_forms.py
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('D,O', [(3, 8), (1, 1), (4, 8), (6, 16)])
+def test_forms_basis_combination_equals_direct_directional_derivatives(D, O):
+    """The derivative is linear in (da, dq): 2 D basis directions combined == nll_directional on the tangents."""
+    T = 257
+    y, var, m0, S0, C, a, q = forms.general_model(2, T, D, O, seed=3)
+    rng = np.random.default_rng(4)
+    da, dq = rng.normal(size=(5, D)), rng.normal(size=(5, D))
+    L, ga, gq = forms.ar1_basis(y[1], var[1], m0[1], S0[1], C[1], a[1], q[1])
+    dA = np.stack([np.diag(v) for v in da])
+    dQ = np.stack([np.diag(v) for v in dq])
+    L2, g2 = c_oracle.nll_directional(y[1], np.maximum(var[1], 1e-12), m0[1], S0[1], np.diag(a[1]), C[1],
+                                      np.diag(q[1]), dA, dQ)
+    assert L == L2
+    scale = np.abs(da) @ np.abs(ga) + np.abs(dq) @ np.abs(gq)      # the sum's terms: what rounding is relative to
+    assert np.all(np.abs(forms.combine(ga, gq, da, dq) - g2) <= 1e-13 * scale)
+
+
+def test_forms_pupil_tangents_are_the_basis_combination():
+    T, seed, u = 700, 12, (0.5, -1.0)
+    ys, ev, m0, S0, lv = forms.chain(T, seed)
+    assert ys.dtype == np.float64 and np.array_equal(ys, ys.astype(np.float32)) and lv.min() >= 0.3
+    L, g = forms.pupil_ref(T, seed, u)
+    Lb, ga, gq = forms.pupil_basis(T, seed, u)
+    _, _, da, dq = forms.pupil_params(u, lv)
+    assert abs(L - Lb) <= 1e-14 * abs(L)
+    np.testing.assert_allclose(forms.combine(ga, gq, da, dq), g, rtol=1e-12, atol=1e-13 * np.abs(g).max())
+
+
+def test_forms_c_and_numpy_routes_agree():
+    """Bars a thousand times under the GPU tests' (1e-9 loss, 1e-8 gradient): the references' own error is no part of
+    what those measure.  Measured on the pupil shape up to T = 140 000: 3e-16 / 1.5e-14."""
+    T, seed = 3001, 13
+    ys, ev, m0, S0, lv = forms.chain(T, seed)
+    for u in forms.US + [(20.0, -20.0), (-20.0, 20.0)]:
+        L1, g1 = orc.pupil_nll_and_grad(np.array(u), ys, m0, S0, orc.PUPIL_C, ev, lv, use_c=False)
+        L2, g2 = forms.pupil_ref(T, seed, u)
+        print(f'routes u={u}: loss {abs(L1 - L2) / abs(L1):.1e} grad {np.abs(g1 - g2).max() / np.abs(g1).max():.1e}')
+        assert abs(L1 - L2) < 1e-12 * abs(L1)
+        np.testing.assert_allclose(g2, g1, rtol=1e-11, atol=1e-12 * np.abs(g1).max())
+    # the general helper's two routes (the NumPy one serves O > 16)
+    y, var, m0, S0, C, a, q = forms.general_model(1, 300, 4, 8, seed=5)
+    Lc, gac, gqc = forms.ar1_basis(y[0], var[0], m0[0], S0[0], C[0], a[0], q[0], use_c=True)
+    Ln, gan, gqn = forms.ar1_basis(y[0], var[0], m0[0], S0[0], C[0], a[0], q[0], use_c=False)
+    assert abs(Lc - Ln) < 1e-12 * abs(Lc)
+    gc, gn = np.concatenate([gac, gqc]), np.concatenate([gan, gqn])
+    np.testing.assert_allclose(gn, gc, rtol=1e-11, atol=1e-12 * np.abs(gc).max())
+
+
+def test_forms_trajectory_helper_is_the_oracle_loop():
+    ys, ev, m0, S0, lv = forms.chain(forms.ADAM_T, 65, False)
+    rec = forms.adam_oracle(65)
+    for cap in (forms.ADAM_CAP, 100, 7):
+        o = orc.pupil_optimize_smooth(ys, m0, S0, orc.PUPIL_C, ev, lv, lr=forms.ADAM_LR, tol=forms.ADAM_TOL,
+                                      safety_cap=cap)
+        it, done, u, last = forms.trajectory_at(rec, cap)
+        s, _ = orc.pupil_to_stable_s(u)
+        assert (float(s[0]), float(s[1]), it, last) == o
+        assert done == (it < cap or bool(rec['stopped'] and len(rec['L']) == cap))
+
+
+def test_forms_mirrors_of_the_host_choices_at_the_cases_shapes():
+    """(frames per lane, units) of dense_wave_run and (chunk, launches) of loss_launch at the GPU cases' shapes."""
+    got = [(forms.dw_chunk_frames(T, K), forms.dw_units(T, K, forms.dw_chunk_frames(T, K)))
+           for K, T in ((3, 9001), (3, 20001), (33, 4097), (1, 131073), (1, 524289), (129, 4097), (3, 40001),
+                        (16, 2050), (2, 5003), (64, 300), (65, 300))]
+    assert got == [(4, 108), (8, 120), (8, 297), (8, 257), (8, 1025), (8, 1161), (8, 237), (4, 144), (2, 80),
+                   (4, 128), (4, 130)]
+    assert [forms.loss_tree(T, n) for T, n in ((1, 6), (513, 6), (600, 6), (40001, 6), (524289, 2), (2050, 1024))] \
+        == [(8, 1), (8, 1), (8, 2), (8, 3), (8, 3), (16, 2)]
+
+
+def test_oracle_quadratic_form_above_16_observations_is_the_same_number():
+    """orc._quad_through takes a three-step contraction above 16 observations; it equals the one-step form."""
+    rng = np.random.default_rng(8)
+    K, O = 4, 20
+    e = rng.normal(size=(K, O))
+    W = rng.normal(size=(K, O, O))
+    Sinv = np.linalg.inv(W @ np.swapaxes(W, 1, 2) + O * np.eye(O))
+    dS = rng.normal(size=(K, O, O))
+    one = np.einsum('ko,kop,kpq,kqr,kr->k', e, Sinv, dS, Sinv, e)
+    scale = np.einsum('ko,kop,kpq,kqr,kr->k', np.abs(e), np.abs(Sinv), np.abs(dS), np.abs(Sinv), np.abs(e))
+    assert np.all(np.abs(orc._quad_through(e, Sinv, dS) - one) <= 1e-14 * scale)
+    assert np.array_equal(orc._quad_through(e[:, :16], Sinv[:, :16, :16], dS[:, :16, :16]),
+                          np.einsum('ko,kop,kpq,kqr,kr->k', e[:, :16], Sinv[:, :16, :16], dS[:, :16, :16],
+                                    Sinv[:, :16, :16], e[:, :16]))
