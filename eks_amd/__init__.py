@@ -21,6 +21,7 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'DifferentiableEmission': 'emission',
         'sample_kalman_posterior': 'posterior', 'sample_singlecam': 'posterior',
         'smooth_increments': 'posterior', 'velocity_singlecam': 'posterior',
+        'process_noise_statistics': 'em', 'refine_smooth_param_em': 'em', 'fit_process_noise_em': 'em',
     }
     if name in table:
         return getattr(importlib.import_module(f'.{table[name]}', __name__), name)

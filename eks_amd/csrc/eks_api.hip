@@ -99,6 +99,86 @@ int eks_smooth_increments(const eks_dims_t* d, const float* y, const float* var,
   return dense_increments(*d, y, var, M, ms, Vs, lag1, dmean, dV, workspace, workspace_bytes, st);
 }
 
+// shapes eks_em_stats takes (EKS_OK) or the status it refuses them with; nothing here touches the device
+static int em_check(const eks_dims_t* d) {
+  const int rc = check_dims(d);
+  if (rc != EKS_OK) return rc;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) {
+    if (!(d->flags & EKS_FLAG_VS_DIAG)) return EKS_ERR_UNSUPPORTED;   // a diagonal Q's M-step reads the diagonal only
+    return diag_em_covers(d->n_frames, d->n_keypoints * d->state_dim) ? EKS_OK : EKS_ERR_SHAPE;
+  }
+  if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
+  // (dense_em_stats' own launch-index check, here so that the workspace query and the call agree)
+  return dense_em_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim) ? EKS_OK : EKS_ERR_SHAPE;
+}
+
+size_t eks_em_stats_workspace_bytes(const eks_dims_t* d) {
+  if (em_check(d) != EKS_OK) return 0;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_em_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
+  return dense_em_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+}
+
+int eks_em_stats(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
+                 const double* A, const double* C, const double* Q, const double* s, double* Sw, void* workspace,
+                 size_t workspace_bytes, eks_stream_t stream) {
+  const int rc = em_check(d);
+  if (rc != EKS_OK) return rc;
+  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s || !Sw) return EKS_ERR_NULL;
+  if (!workspace) return EKS_ERR_WORKSPACE;
+  if (workspace_bytes < eks_em_stats_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (d->flags & EKS_FLAG_DIAG_MODEL) {
+    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
+    return diag_em_stats(*d, y, var, M, Sw, workspace, workspace_bytes, st);
+  }
+  const DenseModel M{m0, S0, A, C, Q, s};
+  return dense_em_stats(*d, y, var, M, Sw, workspace, workspace_bytes, st);
+}
+
+// shapes the M-step for the scale takes: eks_em_stats' with T >= 2 (n = D (T - 1) divides) and, on general models,
+// the full D x D statistic (tr(Q^-1 Sw) needs its off-diagonals)
+static int em_scale_check(const eks_dims_t* d, int32_t n_blocks, int32_t max_iters) {
+  const int rc = em_check(d);
+  if (rc != EKS_OK) return rc;
+  if (d->n_frames < 2 || n_blocks <= 0 || max_iters < 0) return EKS_ERR_SHAPE;
+  if (!(d->flags & EKS_FLAG_DIAG_MODEL) && (d->flags & EKS_FLAG_VS_DIAG)) return EKS_ERR_UNSUPPORTED;
+  return EKS_OK;
+}
+
+int eks_em_scale_step(const eks_dims_t* d, const double* Q, const double* Sw, int32_t n_blocks,
+                      const int32_t* block_offsets, const int32_t* block_members, double lo, double hi, double tol,
+                      int32_t max_iters, double* state, double* s_keypoint, int32_t* n_active, eks_stream_t stream) {
+  const int rc = em_scale_check(d, n_blocks, max_iters);
+  if (rc != EKS_OK) return rc;
+  if (!Q || !Sw || !block_offsets || !block_members || !state || !s_keypoint || !n_active) return EKS_ERR_NULL;
+  return em_scale_step(*d, Q, Sw, n_blocks, block_offsets, block_members, lo, hi, tol, max_iters, state, s_keypoint,
+                       n_active, reinterpret_cast<hipStream_t>(stream));
+}
+
+int eks_em_scale_run(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
+                     const double* A, const double* C, const double* Q, int32_t n_blocks,
+                     const int32_t* block_offsets, const int32_t* block_members, double lo, double hi, double tol,
+                     int32_t max_iters, int32_t n_iters, double* state, double* s_keypoint, double* Sw,
+                     int32_t* n_active, void* workspace, size_t workspace_bytes, eks_stream_t stream) {
+  if (n_iters < 0) return EKS_ERR_SHAPE;
+  const int rc = em_scale_check(d, n_blocks, max_iters);
+  if (rc != EKS_OK) return rc;
+  if (!(d->flags & EKS_FLAG_DIAG_MODEL) && !(d->flags & EKS_FLAG_Q_PD)) return EKS_ERR_UNSUPPORTED;   // Q^-1
+  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !block_offsets || !block_members || !state || !s_keypoint || !Sw ||
+      !n_active)
+    return EKS_ERR_NULL;
+  if (!workspace) return EKS_ERR_WORKSPACE;
+  if (workspace_bytes < eks_em_stats_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
+  for (int it = 0; it < n_iters; ++it) {   // back to back on the stream, no host round trip
+    int rc2 = eks_em_stats(d, y, var, m0, S0, A, C, Q, s_keypoint, Sw, workspace, workspace_bytes, stream);
+    if (rc2 != EKS_OK) return rc2;
+    rc2 = eks_em_scale_step(d, Q, Sw, n_blocks, block_offsets, block_members, lo, hi, tol, max_iters, state, s_keypoint,
+                            n_active, stream);
+    if (rc2 != EKS_OK) return rc2;
+  }
+  return EKS_OK;
+}
+
 int32_t eks_sample_noise_width(const eks_dims_t* d) {
   if (check_dims(d) != EKS_OK) return 0;
   return (d->flags & EKS_FLAG_DIAG_MODEL) ? d->state_dim : d->state_dim + d->obs_dim;

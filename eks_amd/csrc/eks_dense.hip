@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "eks_dense_lane.hpp"
+#include "eks_em_lane.hpp"
 #include "eks_increments_lane.hpp"
 #include "eks_internal.hpp"
 
@@ -501,6 +502,102 @@ int dense_increments(const eks_dims_t& d, const float* y, const float* var, cons
     }
   })
   return hip_status(hipGetLastError());
+}
+
+// ---- eks_em_stats on general models: dense_increments' organisation with the outputs replaced by a sum -----------
+// dense_summarize -> dense_scan -> dense_scan_blocks as they are, then a replay that accumulates the chunk's share of
+// Sw = sum_t E[w_t w_t^T | y] in float64 (eks_em_lane.hpp: dense_em_chunk) into a [chunk][keypoint] plane of D x D
+// (or D, with VS_DIAG) partials behind the generic layout, then eks_em.hip's fixed-order reduce.
+template <int D, typename Obs>
+__global__ __launch_bounds__(64) void dense_em_kernel(DenseGeom G, DenseModelPtrs M, const double* __restrict__ s,
+                                                     Obs obs, const double* __restrict__ pre,
+                                                     const double* __restrict__ suf,
+                                                     const double* __restrict__ bprior,
+                                                     const double* __restrict__ bsuffix, double* __restrict__ filt,
+                                                     double* __restrict__ part, int diag) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.nc) return;
+  constexpr int REC = D + D * D;
+  constexpr int NV = delem_doubles<D>();
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  Vec<double, D> m, eta;
+  Mat<double, D> P, J;
+  // one element per lane (Bs == B): boundaries as in dense_replay_kernel
+  const int blk = j / kDenseCB, ia = j % kDenseCB;
+  const double* rp = bprior + ((size_t)blk * G.K + k) * REC;
+  const double* rs = bsuffix + ((size_t)blk * G.K + k) * REC;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    m.a[a] = rp[a];
+    eta.a[a] = rs[a];
+#pragma unroll
+    for (int b = 0; b < D; ++b) {
+      P.a[a][b] = rp[D + a * D + b];
+      J.a[a][b] = rs[D + a * D + b];
+    }
+  }
+  if (ia > 0) delem_apply(load_delem<double, D>(pre + ((size_t)(j - 1) * G.K + k) * NV), m, P);
+  if (ia + 1 < kDenseCB && j + 1 < G.nc)
+    delem_back(load_delem<double, D>(suf + ((size_t)(j + 1) * G.K + k) * NV), eta, J);
+  if (j == 0) load_prior<D>(M, k, m, P);   // chunk 0 replays frame 0's update of the prior itself
+  const int t0 = j * G.B, len = min(G.B, G.T - t0);
+  const int w = diag ? D : D * D;
+  dense_em_chunk<D, Obs>(obs, k, t0, len, F, sQ, fid, m, P, eta, J, filt + (size_t)t0 * REC * G.K + k, (size_t)G.K,
+                         part + (size_t)idx * w, diag != 0);
+}
+
+static size_t dense_em_part_bytes(int K, int D, int nc) { return align_up((size_t)nc * K * D * D * 8, 256); }
+
+size_t dense_em_workspace_bytes(int T, int K, int D, int O) {
+  if (D < 1 || D > 6 || O < 1 || O > 64) return 0;
+  const int B = dense_chunk(T, K), nc = (T + B - 1) / B;
+  if ((long long)K * nc >= (1 << 30)) return 0;   // dense_em: EKS_ERR_SHAPE
+  return generic_layout(T, K, D, nc, nullptr).bytes + dense_em_part_bytes(K, D, nc);
+}
+
+int dense_em_stats(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double* Sw, void* ws,
+                   size_t ws_bytes, hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
+  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
+  DenseGeom G{K, T, O, dense_chunk(T, K), 0, 0, 0};
+  G.nc = (T + G.B - 1) / G.B;
+  G.Bs = G.B;
+  G.ncs = G.nc;
+  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
+  if (ws_bytes < dense_em_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
+  const int nblk = (G.nc + kDenseCB - 1) / kDenseCB, lanes = K * G.nc;
+  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
+  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
+  double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + L.bytes);
+  const int diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
+  const Gate open{nullptr, 0.0};
+  EKS_DISPATCH_D(D, {
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
+    {
+      ProfScope ps("dense_em_summarize", st);
+      hipLaunchKernelGGL((dense_summarize_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
+                         Mm.s, obs, L.elems, L.first, open);
+    }
+    {
+      ProfScope ps("dense_em_scan", st);
+      hipLaunchKernelGGL(dense_scan_kernel<DD>, dim3(K, nblk), dim3(2 * kDenseCB), 0, st, G, L.elems, L.pre, L.suf,
+                         L.agg, open);
+      hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk, L.first, L.agg,
+                         L.bprior, L.bsuffix, open);
+    }
+    {
+      ProfScope ps("dense_em_replay", st);
+      hipLaunchKernelGGL((dense_em_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s,
+                         obs, L.pre, L.suf, L.bprior, L.bsuffix, L.filt, part, diag);
+    }
+  })
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_status(e);
+  // partials [chunk][keypoint][w]: column (k, entry) of the reduce is Sw's own flat index
+  return em_reduce(part, G.nc, K * (diag ? D : D * D), Sw, st);
 }
 
 // ---- SCORE form: the optimiser's loss and its derivative from the smoother's own kernels ---------------

@@ -125,6 +125,19 @@ int diag_increments(const eks_dims_t& d, const float* y, const float* var, const
 size_t dense_increments_workspace_bytes(int T, int K, int D, int O);
 int dense_increments(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, float* ms, float* Vs,
                      float* lag1, float* dmean, float* dV, void* ws, size_t ws_bytes, hipStream_t st);
+// E-step statistic Sw = sum_t E[w_t w_t^T | y] and the M-step for the scale (eks_em.hip: scalar chains, the
+// fixed-order reduce of the chunk partials and the step; eks_dense.hip: general models, always the generic kernels)
+bool diag_em_covers(int T, int N);
+size_t diag_em_workspace_bytes(int T, int N);
+int diag_em_stats(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double* Sw, void* ws,
+                  size_t ws_bytes, hipStream_t st);
+size_t dense_em_workspace_bytes(int T, int K, int D, int O);
+int dense_em_stats(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double* Sw, void* ws,
+                   size_t ws_bytes, hipStream_t st);
+int em_reduce(const double* part, int nc, int ne, double* Sw, hipStream_t st);
+int em_scale_step(const eks_dims_t& d, const double* Q, const double* Sw, int n_blocks, const int32_t* offs,
+                  const int32_t* members, double lo, double hi, double tol, int max_iters, double* state,
+                  double* s_keypoint, int32_t* n_active, hipStream_t st);
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M,
                  float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);

@@ -234,6 +234,69 @@ def smooth_increments(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool 
     return out
 
 
+def _em_args(y, var, m0, S0, A, C, Q):
+    T, K, O = y.shape
+    D = m0.shape[-1]
+    return (T, K, O, D), [_chk(y, torch.float32, 'y'), _chk(var, torch.float32, 'var', (T, K, O)),
+                          _chk(m0, torch.float64, 'm0', (K, D)), _chk(S0, torch.float64, 'S0', (K, D, D)),
+                          _chk(A, torch.float64, 'A', (K, D, D)), _chk(C, torch.float64, 'C', (K, O, D)),
+                          _chk(Q, torch.float64, 'Q', (K, D, D))]
+
+
+def em_stats(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False):
+    """eks_em_stats: Sw = sum_t E[w_t w_t' | y] of the model eks_smooth runs, float64 (K, D) with vs_diag (the only
+    form on scalar chains, FLAG_DIAG_MODEL) or (K, D, D)."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
+    s = _chk(s, torch.float64, 's', (K,))
+    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
+    dims = _dims(K, T, D, O, flags)
+    Sw = torch.empty((K, D) if vs_diag else (K, D, D), dtype=torch.float64, device=y.device)
+    ws = _workspace(lib.eks_em_stats_workspace_bytes(ctypes.byref(dims)), y.device)
+    rc = lib.eks_em_stats(ctypes.byref(dims), *[_ptr(b) for b in bufs], _ptr(s), _ptr(Sw), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, 'eks_em_stats')
+    return Sw
+
+
+class EmScaleLoop:
+    """eks_em_scale_run with every buffer allocated once: `run(n)` enqueues n iterations of E-step + M-step for the
+    scale without touching the host.  state (n_blocks, 4) float64 = {log s, last |delta log s|, iterations, done};
+    s_keypoint (K,) float64 is read by the first E-step and rewritten by every M-step.  Sw is (K, D) on scalar chains
+    and (K, D, D) on general models (VS_DIAG is set / cleared accordingly)."""
+
+    def __init__(self, y, var, m0, S0, A, C, Q, block_offsets, block_members, state, s_keypoint, lo, hi, tol,
+                 max_iters, flags: int = 0):
+        self.lib = _lib.load()
+        (T, K, O, D), self.bufs = _em_args(y, var, m0, S0, A, C, Q)
+        self.offs = _chk(block_offsets, torch.int32, 'block_offsets')
+        self.members = _chk(block_members, torch.int32, 'block_members', (K,))
+        self.nb = self.offs.numel() - 1
+        self.state = _chk(state, torch.float64, 'state', (self.nb, 4))
+        self.s_keypoint = _chk(s_keypoint, torch.float64, 's_keypoint', (K,))
+        self.opt = (float(lo), float(hi), float(tol), int(max_iters))
+        diag = bool(flags & FLAG_DIAG_MODEL)
+        flags = (flags | FLAG_VS_DIAG) if diag else (flags & ~FLAG_VS_DIAG)
+        self.dims = _dims(K, T, D, O, flags)
+        dev = y.device
+        self.Sw = torch.zeros((K, D) if diag else (K, D, D), dtype=torch.float64, device=dev)
+        self.n_active = torch.full((1,), self.nb, dtype=torch.int32, device=dev)
+        self.ws = _workspace(self.lib.eks_em_stats_workspace_bytes(ctypes.byref(self.dims)), dev)
+
+    def run(self, n_iters: int) -> None:
+        rc = self.lib.eks_em_scale_run(ctypes.byref(self.dims), *[_ptr(b) for b in self.bufs], self.nb, _ptr(self.offs),
+                                       _ptr(self.members), *self.opt, int(n_iters), _ptr(self.state),
+                                       _ptr(self.s_keypoint), _ptr(self.Sw), _ptr(self.n_active), _ptr(self.ws),
+                                       self.ws.numel(), _stream())
+        _lib.check(rc, 'eks_em_scale_run')
+
+    def step(self) -> None:
+        """eks_em_scale_step alone, on the Sw the object holds."""
+        rc = self.lib.eks_em_scale_step(ctypes.byref(self.dims), _ptr(self.bufs[6]), _ptr(self.Sw), self.nb,
+                                        _ptr(self.offs), _ptr(self.members), *self.opt, _ptr(self.state),
+                                        _ptr(self.s_keypoint), _ptr(self.n_active), _stream())
+        _lib.check(rc, 'eks_em_scale_step')
+
+
 def sample_noise_width(D: int, O: int, flags: int) -> int:
     """eks_sample_noise_width: standard normals consumed per (draw, frame, keypoint)."""
     return int(_lib.load().eks_sample_noise_width(ctypes.byref(_dims(1, 1, D, O, flags))))

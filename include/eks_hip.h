@@ -139,6 +139,46 @@ int eks_smooth_increments(const eks_dims_t* dims, const float* y, const float* v
                           float* ms, float* Vs, float* lag1, float* dmean, float* dV, void* workspace,
                           size_t workspace_bytes, eks_stream_t stream);
 
+/* ---- EM on the model eks_smooth runs (time-varying R = diag(max(var_t, 1e-12))).  No reference counterpart: the
+ * reference fits s to a constant-R filter likelihood.  dims, flags and inputs are those of eks_smooth.
+ * E-step statistic, per keypoint: the smoothed second moment of the process noise
+ *   Sw = sum_{t=0}^{T-2} E[ w_t w_t^T | y ],   w_t = x_{t+1} - A x_t,
+ * formed inside the RTS step as a sum of non-negative terms (eks_amd/csrc/eks_em_lane.hpp), summed in float64 in a
+ * fixed order without floating-point atomics: two calls give the same bits, and on scalar chains a call on a subset
+ * of the keypoints gives that subset's bits.  By Fisher's identity, with n = D (T - 1),
+ *   d loglik / d log s = (tr(Q^-1 Sw) / s - n) / 2       (loglik: the filter's, with the time-varying R).
+ *   Sw float64: scalar chains (EKS_FLAG_DIAG_MODEL) [K][D], the diagonal - all a diagonal Q's M-step reads; the
+ *     off-diagonal sums of E w_a E w_b are not formed - and the call exists with EKS_FLAG_VS_DIAG only
+ *     (EKS_ERR_UNSUPPORTED without); the filter and the RTS step are eks_smooth's float32 ones, nothing of length T
+ *     is written.  General models: [K][D][D], or [K][D] diagonals with EKS_FLAG_VS_DIAG; D <= 6 and O <= 64 (else
+ *     EKS_ERR_UNSUPPORTED), float64 throughout, only Pp is factored so a singular Q or S0 is fine.
+ *   T == 1 gives zeros.  A shape whose launches would index threads beyond an int is EKS_ERR_SHAPE.  Every refusal
+ *   is returned before anything is enqueued, and the workspace query returns 0 for refused shapes.
+ * M-step for the scale s with Q fixed (eks_em_scale_step, one thread per block of keypoints sharing one s; blocks
+ * in CSR form as for eks_adam_step):  s_new = sum_members tr(Q^-1 Sw) / sum_members n, on log s clipped to
+ * [lo, hi]; done = |delta log s| < tol; each step cannot decrease the likelihood.
+ *   state float64 [n_blocks][4] = {log s, last |delta log s|, iterations, done}: the caller sets {log s0, 0, 0, 0}
+ *   and s_keypoint[k] = s0 of k's block.  Blocks that are done or at max_iters are left untouched.  The step writes
+ *   s_keypoint [K] for the next E-step and *n_active = the number of blocks still running.
+ *   Sw as eks_em_stats writes it: [K][D] on scalar chains (Q^-1 = 1 / q_i), [K][D][D] on general models (Q^-1 by
+ *   Cholesky; EKS_FLAG_VS_DIAG there is EKS_ERR_UNSUPPORTED: the trace needs the off-diagonals).
+ * eks_em_scale_run enqueues n_iters x { eks_em_stats at s_keypoint -> eks_em_scale_step } back to back, no host
+ * round trip; workspace as eks_em_stats.  Both refuse T < 2 with EKS_ERR_SHAPE (n = 0); the run refuses general
+ * models without EKS_FLAG_Q_PD with EKS_ERR_UNSUPPORTED.  EM is slow when the optimum is far from the start: these
+ * calls REFINE an s that is already close (eks_adam_run's). -------------------------------------------------------- */
+size_t eks_em_stats_workspace_bytes(const eks_dims_t* dims);
+int eks_em_stats(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,
+                 const double* A, const double* C, const double* Q, const double* s, double* Sw, void* workspace,
+                 size_t workspace_bytes, eks_stream_t stream);
+int eks_em_scale_step(const eks_dims_t* dims, const double* Q, const double* Sw, int32_t n_blocks,
+                      const int32_t* block_offsets, const int32_t* block_members, double lo, double hi, double tol,
+                      int32_t max_iters, double* state, double* s_keypoint, int32_t* n_active, eks_stream_t stream);
+int eks_em_scale_run(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,
+                     const double* A, const double* C, const double* Q, int32_t n_blocks,
+                     const int32_t* block_offsets, const int32_t* block_members, double lo, double hi, double tol,
+                     int32_t max_iters, int32_t n_iters, double* state, double* s_keypoint, double* Sw,
+                     int32_t* n_active, void* workspace, size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- constant observation noise for the loss: eks/core.py:702-709
  * rconst[k][o] = max(nanmedian_t max(var[t][k][o], 1e-12), min_var)  (float64 out) ----------- */
 size_t eks_const_r_workspace_bytes(const eks_dims_t* dims);

@@ -1,0 +1,126 @@
+"""eks_em_stats against eks_smooth and against the route to the same number without it, on the C3 shape
+(100 000 frames x 256 keypoints, D = 2, diagonal, unit A and C, VS_DIAG), in the same process, alternating:
+
+    (a) eks_smooth with VS_DIAG                               ms, Vs
+    (b) eks_smooth_increments with dmean, dV only, then the torch reduction sum_t dmean^2 + dV in float64
+        (with A = I the process noise IS the increment: the way to Sw before eks_em_stats existed)
+    (c) eks_em_stats                                          Sw
+    (d) one iteration of eks_em_scale_run                     E-step + M-step for the scale
+
+    python tools/em_time.py [--frames 100000] [--keypoints 256] [--reps 20] [--out FILE]
+
+Prints one JSON line: median milliseconds of the four (device events), (c)/(a), (c)/(b), the per-kernel split of one
+profiled call of (a), (b)'s kernels, (c) and (d) (eks_profile_enable), and how far (b) and (c) disagree.  On a shared
+box run it under a time limit of its own:
+
+    timeout -k 10 300 python tools/em_time.py --out profiles/em_time.json"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--frames', type=int, default=100000)
+    ap.add_argument('--keypoints', type=int, default=256)
+    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    import torch
+    from eks_amd import _lib, hip_ops
+    dev = hip_ops.require_gpu()
+    lib = _lib.load()
+    T, K, D = a.frames, a.keypoints, 2
+    g = torch.Generator(device=dev).manual_seed(0)
+    y = torch.cumsum(torch.randn((T, K, D), device=dev, generator=g), dim=0).contiguous()
+    var = torch.exp(torch.randn((T, K, D), device=dev, generator=g)).contiguous()
+    eye = torch.eye(D, dtype=torch.float64, device=dev).repeat(K, 1, 1).contiguous()
+    m0 = torch.zeros((K, D), dtype=torch.float64, device=dev)
+    S0 = eye * 4.0
+    s = torch.full((K,), 2.0, dtype=torch.float64, device=dev)
+    flags = _lib.FLAG_DIAG_MODEL | _lib.FLAG_UNIT_AC
+    smooth = hip_ops.PreparedSmooth(y, var, m0, S0, eye, eye.clone(), eye.clone(), s, flags, vs_diag=True)
+    # (b), (c) with everything but the launches done once, like PreparedSmooth: the comparison is of device time
+    dims = _lib.EksDims(K, T, D, D, flags | _lib.FLAG_VS_DIAG)
+    p = lambda t: ctypes.c_void_p(0 if t is None else t.data_ptr())
+    model = (p(y), p(var), p(m0), p(S0), p(eye), p(eye), p(eye))
+    dmean, dV = (torch.empty((T, K, D), dtype=torch.float32, device=dev) for _ in range(2))
+    ws_b = torch.empty(max(int(lib.eks_smooth_increments_workspace_bytes(ctypes.byref(dims))), 256), dtype=torch.uint8,
+                       device=dev)
+    inc_args = (ctypes.byref(dims), *model, p(s), None, None, None, p(dmean), p(dV), p(ws_b), ws_b.numel())
+    Sw = torch.empty((K, D), dtype=torch.float64, device=dev)
+    ws_c = torch.empty(max(int(lib.eks_em_stats_workspace_bytes(ctypes.byref(dims))), 256), dtype=torch.uint8, device=dev)
+    em_args = (ctypes.byref(dims), *model, p(s), p(Sw), p(ws_c), ws_c.numel())
+    ar = torch.arange(K + 1, dtype=torch.int32, device=dev)
+    state = torch.zeros((K, 4), dtype=torch.float64, device=dev)
+    state[:, 0] = float(np.log(2.0))
+    loop = hip_ops.EmScaleLoop(y, var, m0, S0, eye, eye.clone(), eye.clone(), ar, ar[:K].contiguous(), state, s.clone(),
+                               -8.0, 8.0, 0.0, 1 << 30, flags=flags)
+    box = {}
+
+    def via_increments():
+        _lib.check(lib.eks_smooth_increments(*inc_args, hip_ops._stream()), 'eks_smooth_increments')
+        box['b'] = (dmean.double().square() + dV.double()).sum(dim=0)
+
+    def em_stats():
+        _lib.check(lib.eks_em_stats(*em_args, hip_ops._stream()), 'eks_em_stats')
+
+    def em_iteration():
+        loop.run(1)
+
+    def timed(fn):
+        a_, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a_.record()
+        fn()
+        b_.record()
+        b_.synchronize()
+        return a_.elapsed_time(b_)
+
+    fns = (smooth, via_increments, em_stats, em_iteration)
+    for _ in range(3):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    disagreement = float(((box['b'] - Sw).abs() / Sw).max())
+    times = [[] for _ in fns]
+    for _ in range(a.reps):                       # alternating: all four see the same neighbours on the box
+        for t, fn in zip(times, fns):
+            t.append(timed(fn))
+
+    def split_of(fn):
+        lib.eks_profile_enable(1)
+        fn()
+        torch.cuda.synchronize()
+        names = ctypes.create_string_buffer(4096)
+        ms = (ctypes.c_float * 64)()
+        n = lib.eks_profile_drain(names, 4096, ms, 64)
+        lib.eks_profile_enable(0)
+        return dict(zip([x.decode() for x in names.raw.split(b'\0')[:n]], [round(float(ms[i]), 4) for i in range(n)]))
+
+    splits = [split_of(fn) for fn in fns]
+    med = [float(np.median(t)) for t in times]
+    rng = lambda t: [round(min(t), 4), round(max(t), 4)]
+    res = dict(tool='em_time', frames=T, keypoints=K, reps=a.reps,
+               smooth_ms=round(med[0], 4), smooth_ms_min_max=rng(times[0]),
+               increments_then_torch_ms=round(med[1], 4), increments_then_torch_ms_min_max=rng(times[1]),
+               em_stats_ms=round(med[2], 4), em_stats_ms_min_max=rng(times[2]),
+               em_iteration_ms=round(med[3], 4), em_iteration_ms_min_max=rng(times[3]),
+               em_stats_over_smooth=round(med[2] / med[0], 3), em_stats_over_increments_then_torch=round(med[2] / med[1], 3),
+               sw_relative_disagreement_b_c=disagreement,
+               smooth_kernels_ms=splits[0], increments_kernels_ms=splits[1], em_stats_kernels_ms=splits[2],
+               em_iteration_kernels_ms=splits[3])
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
