@@ -1047,10 +1047,17 @@ int order_stats(int T, int N, const float* x, int r_lo, int r_hi, float* out, in
 }
 
 // ==========================================================================================
-// argmin over candidates (first minimum, numpy.argmin semantics) + gather of s
+// argmin over candidates (numpy.argmin semantics: the first minimum, a NaN is the minimum) + gather of s
 // ==========================================================================================
-// one wave per keypoint: lanes stride over the candidates, (value, index) min-reduction that
-// keeps the FIRST minimum (numpy.argmin semantics)
+// (value v at index c) comes before (bv at bc) in numpy.argmin's order: a NaN is smaller than every number, equal
+// values and NaNs among themselves go by index
+__device__ __forceinline__ bool argmin_before(double v, int c, double bv, int bc) {
+  const bool vn = v != v, bn = bv != bv;
+  if (vn || bn) return vn && (!bn || c < bc);
+  return v < bv || (v == bv && c < bc);
+}
+
+// one wave per keypoint: lanes stride over the candidates, (value, index) min-reduction in that order
 __global__ __launch_bounds__(256) void argmin_kernel(int K, int n_cand, const double* __restrict__ nll,
                                                     const double* __restrict__ s_cand,
                                                     double* __restrict__ s_out,
@@ -1064,7 +1071,7 @@ __global__ __launch_bounds__(256) void argmin_kernel(int K, int n_cand, const do
   int best = kNone;
   for (int c = lane; c < n_cand; c += 64) {
     const double v = row[c];
-    if (best == kNone || v < bv) {
+    if (best == kNone || argmin_before(v, c, bv, best)) {
       bv = v;
       best = c;
     }
@@ -1073,7 +1080,7 @@ __global__ __launch_bounds__(256) void argmin_kernel(int K, int n_cand, const do
   for (int off = 32; off >= 1; off >>= 1) {
     const double ov = __shfl_xor(bv, off);
     const int oi = __shfl_xor(best, off);
-    if (oi != kNone && (best == kNone || ov < bv || (ov == bv && oi < best))) {
+    if (oi != kNone && (best == kNone || argmin_before(ov, oi, bv, best))) {
       bv = ov;
       best = oi;
     }

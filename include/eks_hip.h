@@ -225,8 +225,9 @@ int eks_np_nanstd_rows(int32_t n_rows, int32_t n_cols, const float* x, const int
 int eks_np_nanstd_diff_rows(int32_t n_frames, int32_t n_keypoints, int32_t obs_dim, const float* x, const int32_t* leaves,
                             int32_t n_leaves, const int32_t* ops, int32_t n_ops, float* out, eks_stream_t stream);
 
-/* ---- argmin over candidates + gather: s_out[k] = s_cand[argmin_c nll[k][c]] (first minimum,
- * like numpy.argmin).  idx_out (optional) receives the int32 indices. ---------------------- */
+/* ---- argmin over candidates + gather: s_out[k] = s_cand[argmin_c nll[k][c]], numpy.argmin's rule: the first
+ * minimum (ties, +0 / -0 included, go to the lower index), and a NaN counts as smaller than every number, so a row
+ * with NaNs gives the index of its first NaN.  idx_out (optional) receives the int32 indices. ---------------------- */
 int eks_argmin_s(int32_t n_keypoints, int32_t n_cand, const double* nll, const double* s_cand,
                  double* s_out, int32_t* idx_out, eks_stream_t stream);
 
