@@ -22,6 +22,8 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'sample_kalman_posterior': 'posterior', 'sample_singlecam': 'posterior',
         'smooth_increments': 'posterior', 'velocity_singlecam': 'posterior',
         'process_noise_statistics': 'em', 'refine_smooth_param_em': 'em', 'fit_process_noise_em': 'em',
+        'filter_innovations': 'diagnostics', 'log_likelihood': 'diagnostics', 'innovation_summary': 'diagnostics',
+        'innovations_singlecam': 'diagnostics',
     }
     if name in table:
         return getattr(importlib.import_module(f'.{table[name]}', __name__), name)

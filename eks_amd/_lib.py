@@ -41,6 +41,8 @@ SIGNATURES = {
     'eks_em_scale_run': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 7 + [c_int32, c_void_p, c_void_p, c_double,
                                                                              c_double, c_double, c_int32, c_int32]
                          + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    'eks_innovations_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
+    'eks_innovations': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 14 + [c_size_t, c_void_p]),
     'eks_sample_noise_width': (c_int32, [POINTER(EksDims)]),
     'eks_sample_workspace_bytes': (c_size_t, [POINTER(EksDims), c_int32]),
     'eks_sample': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 8 + [c_int32, ctypes.c_uint64, c_int32, c_int32]

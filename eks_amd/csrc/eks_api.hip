@@ -135,6 +135,45 @@ int eks_em_stats(const eks_dims_t* d, const float* y, const float* var, const do
   return dense_em_stats(*d, y, var, M, Sw, workspace, workspace_bytes, st);
 }
 
+// shapes eks_innovations takes (EKS_OK) or the status it refuses them with; nothing here touches the device.
+// EKS_FLAG_VS_DIAG is ignored: no output is a covariance matrix
+static int innovations_check(const eks_dims_t* d) {
+  const int rc = check_dims(d);
+  if (rc != EKS_OK) return rc;
+  if (d->flags & EKS_FLAG_DIAG_MODEL)
+    return diag_em_covers(d->n_frames, d->n_keypoints * d->state_dim) ? EKS_OK : EKS_ERR_SHAPE;
+  if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
+  return dense_innovations_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim) ? EKS_OK
+                                                                                                    : EKS_ERR_SHAPE;
+}
+
+size_t eks_innovations_workspace_bytes(const eks_dims_t* d) {
+  if (innovations_check(d) != EKS_OK) return 0;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_em_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
+  return dense_innovations_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+}
+
+int eks_innovations(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
+                    const double* A, const double* C, const double* Q, const double* s, float* innov,
+                    float* innov_var, float* nis, float* frame_ll, double* loglik, void* workspace,
+                    size_t workspace_bytes, eks_stream_t stream) {
+  const int rc = innovations_check(d);
+  if (rc != EKS_OK) return rc;
+  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s) return EKS_ERR_NULL;
+  if (!innov && !innov_var && !nis && !frame_ll && !loglik) return EKS_ERR_NULL;
+  // scalar chains: nis and frame_ll are elementwise functions of innov and innov_var
+  if ((d->flags & EKS_FLAG_DIAG_MODEL) && (nis || frame_ll)) return EKS_ERR_UNSUPPORTED;
+  if (!workspace) return EKS_ERR_WORKSPACE;
+  if (workspace_bytes < eks_innovations_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (d->flags & EKS_FLAG_DIAG_MODEL) {
+    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
+    return diag_innovations(*d, y, var, M, innov, innov_var, loglik, workspace, workspace_bytes, st);
+  }
+  const DenseModel M{m0, S0, A, C, Q, s};
+  return dense_innovations(*d, y, var, M, innov, innov_var, nis, frame_ll, loglik, workspace, workspace_bytes, st);
+}
+
 // shapes the M-step for the scale takes: eks_em_stats' with T >= 2 (n = D (T - 1) divides) and, on general models,
 // the full D x D statistic (tr(Q^-1 Sw) needs its off-diagonals)
 static int em_scale_check(const eks_dims_t* d, int32_t n_blocks, int32_t max_iters) {

@@ -18,6 +18,7 @@
 #include "eks_dense_lane.hpp"
 #include "eks_em_lane.hpp"
 #include "eks_increments_lane.hpp"
+#include "eks_innov_lane.hpp"
 #include "eks_internal.hpp"
 
 namespace eks {
@@ -598,6 +599,92 @@ int dense_em_stats(const eks_dims_t& d, const float* y, const float* var, const 
   if (e != hipSuccess) return hip_status(e);
   // partials [chunk][keypoint][w]: column (k, entry) of the reduce is Sw's own flat index
   return em_reduce(part, G.nc, K * (diag ? D : D * D), Sw, st);
+}
+
+// ---- eks_innovations on general models: dense_em's organisation, forward only ------------------------------------
+// dense_summarize -> dense_scan -> dense_scan_blocks as they are, then a replay that walks every chunk forwards from
+// the belief that entered it (eks_innov_lane.hpp: dense_innov_chunk): innovations, their variances, nis and the
+// frame's log-likelihood stream out, the chunk's log-likelihood goes to a [chunk][keypoint] plane behind the generic
+// layout (which carries no filtered-belief stream here), then eks_em.hip's fixed-order reduce.
+template <int D, typename Obs>
+__global__ __launch_bounds__(64) void dense_innov_kernel(DenseGeom G, DenseModelPtrs M, const double* __restrict__ s,
+                                                        Obs obs, const double* __restrict__ pre,
+                                                        const double* __restrict__ bprior, DenseInnovOut out,
+                                                        double* __restrict__ part) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.nc) return;
+  constexpr int REC = D + D * D;
+  constexpr int NV = delem_doubles<D>();
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  Vec<double, D> m;
+  Mat<double, D> P;
+  // one element per lane (Bs == B): the forward boundary as in dense_replay_kernel
+  const int blk = j / kDenseCB, ia = j % kDenseCB;
+  const double* rp = bprior + ((size_t)blk * G.K + k) * REC;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    m.a[a] = rp[a];
+#pragma unroll
+    for (int b = 0; b < D; ++b) P.a[a][b] = rp[D + a * D + b];
+  }
+  if (ia > 0) delem_apply(load_delem<double, D>(pre + ((size_t)(j - 1) * G.K + k) * NV), m, P);
+  if (j == 0) load_prior<D>(M, k, m, P);   // chunk 0 replays frame 0's update of the prior itself
+  const int t0 = j * G.B, len = min(G.B, G.T - t0);
+  const double ll = dense_innov_chunk<D, Obs>(obs, G.K, G.O, k, t0, len, F, sQ, fid, m, P, out);
+  if (part) part[idx] = ll;
+}
+
+size_t dense_innovations_workspace_bytes(int T, int K, int D, int O) {
+  if (D < 1 || D > 6 || O < 1 || O > 64) return 0;
+  const int B = dense_chunk(T, K), nc = (T + B - 1) / B;
+  if ((long long)K * nc >= (1 << 30)) return 0;   // dense_innovations: EKS_ERR_SHAPE
+  return generic_layout(0, K, D, nc, nullptr).bytes + align_up((size_t)nc * K * 8, 256);
+}
+
+int dense_innovations(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, float* innov,
+                      float* innov_var, float* nis, float* frame_ll, double* loglik, void* ws, size_t ws_bytes,
+                      hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
+  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
+  DenseGeom G{K, T, O, dense_chunk(T, K), 0, 0, 0};
+  G.nc = (T + G.B - 1) / G.B;
+  G.Bs = G.B;
+  G.ncs = G.nc;
+  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
+  if (ws_bytes < dense_innovations_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
+  const int nblk = (G.nc + kDenseCB - 1) / kDenseCB, lanes = K * G.nc;
+  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
+  const GenericLayout L = generic_layout(0, K, D, G.nc, static_cast<char*>(ws));
+  double* part = loglik ? reinterpret_cast<double*>(static_cast<char*>(ws) + L.bytes) : nullptr;
+  const DenseInnovOut out{innov, innov_var, nis, frame_ll};
+  const Gate open{nullptr, 0.0};
+  EKS_DISPATCH_D(D, {
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
+    {
+      ProfScope ps("dense_innov_summarize", st);
+      hipLaunchKernelGGL((dense_summarize_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
+                         Mm.s, obs, L.elems, L.first, open);
+    }
+    {
+      ProfScope ps("dense_innov_scan", st);
+      hipLaunchKernelGGL(dense_scan_kernel<DD>, dim3(K, nblk), dim3(2 * kDenseCB), 0, st, G, L.elems, L.pre, L.suf,
+                         L.agg, open);
+      hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk, L.first, L.agg,
+                         L.bprior, L.bsuffix, open);
+    }
+    {
+      ProfScope ps("dense_innov_replay", st);
+      hipLaunchKernelGGL((dense_innov_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s,
+                         obs, L.pre, L.bprior, out, part);
+    }
+  })
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_status(e);
+  if (!loglik) return EKS_OK;
+  return em_reduce(part, G.nc, K, loglik, st);   // partials [chunk][keypoint]
 }
 
 // ---- SCORE form: the optimiser's loss and its derivative from the smoother's own kernels ---------------

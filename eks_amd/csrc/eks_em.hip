@@ -13,27 +13,10 @@
 #include <hip/hip_runtime.h>
 
 #include "eks_em_lane.hpp"
+#include "eks_em_plan.hpp"
 #include "eks_internal.hpp"
 
 namespace eks {
-
-constexpr int kEmChunk = 32;   // frames per lane: 2 * B VGPRs hold (mf, Pf) of the chunk in E2
-
-// lanes along chains; N < 64 packs 64 / NT chunks of NT = pow2ceil(N) chains into a wave (as eks_increments.hip)
-struct EmMap {
-  int nt_log2;
-  int ntile;     // ceil(N / NT)
-};
-
-__device__ __forceinline__ bool em_coords(const EmMap& L, int N, int nc, int& n, int& j) {
-  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int tile = wave % L.ntile, cg = wave / L.ntile;
-  const int nt = 1 << L.nt_log2;
-  n = tile * nt + (lane & (nt - 1));
-  j = cg * (64 >> L.nt_log2) + (lane >> L.nt_log2);
-  return n < N && j < nc;
-}
 
 template <int B, bool UNIT>
 __global__ __launch_bounds__(256) void em_summarize_kernel(EmMap L, SampleWs W, DiagModel M, SampleCall c) {
@@ -121,12 +104,14 @@ size_t diag_em_workspace_bytes(int T, int N) {
   return 9 * plane(nc, N) + 9 * plane(ng, N) + plane64(nc, N);
 }
 
-int diag_em_stats(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double* Sw, void* ws,
-                  size_t ws_bytes, hipStream_t st) {
+// E1 + S1 on the caller's workspace: the planes of W (W.pm, W.pP: predicted belief entering every chunk; W.sEta, W.sJ:
+// information after it), the lane mapping and the float64 plane of chunk partials behind them.  Also the first two
+// passes of eks_innovations (eks_innov.hip).
+int diag_em_forward(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, void* ws, EmPlan& E,
+                    hipStream_t st) {
   const int T = d.n_frames, N = d.n_keypoints * d.state_dim;
-  if (!diag_em_covers(T, N)) return EKS_ERR_SHAPE;
-  if (ws_bytes < diag_em_workspace_bytes(T, N)) return EKS_ERR_WORKSPACE;
-  SampleWs W{};
+  SampleWs& W = E.W;
+  W = SampleWs{};
   em_geometry(T, W.nc, W.gs, W.ng);
   W.N = N;
   W.n_draws = 0;
@@ -140,17 +125,17 @@ int diag_em_stats(const eks_dims_t& d, const float* y, const float* var, const D
   W.pm = take(W.nc); W.pP = take(W.nc); W.sEta = take(W.nc); W.sJ = take(W.nc);
   W.gA = take(W.ng); W.gb = take(W.ng); W.gC = take(W.ng); W.gEta = take(W.ng); W.gJ = take(W.ng);
   W.gm = take(W.ng); W.gP = take(W.ng); W.gsEta = take(W.ng); W.gsJ = take(W.ng);
-  double* part = reinterpret_cast<double*>(at);
+  E.part = reinterpret_cast<double*>(at);
 
-  EmMap L;
+  EmMap& L = E.L;
   L.nt_log2 = 0;
   while ((1 << L.nt_log2) < N && L.nt_log2 < 6) ++L.nt_log2;
   L.ntile = (N + (1 << L.nt_log2) - 1) >> L.nt_log2;
   const int cpw = 64 >> L.nt_log2;                               // chunks per wave
   const long waves = (long)L.ntile * ((W.nc + cpw - 1) / cpw);
-  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  E.grid = dim3((unsigned)((waves + 3) / 4));
+  const dim3 grid = E.grid, block(256);
   const SampleCall cs{y, var, nullptr, nullptr, nullptr, T, 0u, 0u, 0u, 0u};
-  const EmCall c{y, var, part, T};
   const bool unit = (d.flags & EKS_FLAG_UNIT_AC) != 0;
   constexpr int B = kEmChunk;
   const unsigned gN = (unsigned)(((size_t)W.ng * N + 255) / 256);
@@ -166,12 +151,25 @@ int diag_em_stats(const eks_dims_t& d, const float* y, const float* var, const D
     hipLaunchKernelGGL(em_scan_kernel, dim3((N + 63) / 64), dim3(64), 0, st, W, M);
     hipLaunchKernelGGL(em_scan_apply_kernel, dim3(gN), dim3(256), 0, st, W);
   }
+  return hip_status(hipGetLastError());
+}
+
+int diag_em_stats(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double* Sw, void* ws,
+                  size_t ws_bytes, hipStream_t st) {
+  const int T = d.n_frames, N = d.n_keypoints * d.state_dim;
+  if (!diag_em_covers(T, N)) return EKS_ERR_SHAPE;
+  if (ws_bytes < diag_em_workspace_bytes(T, N)) return EKS_ERR_WORKSPACE;
+  EmPlan E;
+  const int rc = diag_em_forward(d, y, var, M, ws, E, st);
+  if (rc != EKS_OK) return rc;
+  const EmCall c{y, var, E.part, T};
   {
     ProfScope ps("em_replay", st);
-    if (unit) hipLaunchKernelGGL((em_replay_kernel<B, true>), grid, block, 0, st, L, W, M, c);
-    else hipLaunchKernelGGL((em_replay_kernel<B, false>), grid, block, 0, st, L, W, M, c);
+    if (d.flags & EKS_FLAG_UNIT_AC)
+      hipLaunchKernelGGL((em_replay_kernel<kEmChunk, true>), E.grid, dim3(256), 0, st, E.L, E.W, M, c);
+    else hipLaunchKernelGGL((em_replay_kernel<kEmChunk, false>), E.grid, dim3(256), 0, st, E.L, E.W, M, c);
   }
-  return em_reduce(part, W.nc, N, Sw, st);
+  return em_reduce(E.part, E.W.nc, N, Sw, st);
 }
 
 // ==================================================================================================================

@@ -138,6 +138,14 @@ int em_reduce(const double* part, int nc, int ne, double* Sw, hipStream_t st);
 int em_scale_step(const eks_dims_t& d, const double* Q, const double* Sw, int n_blocks, const int32_t* offs,
                   const int32_t* members, double lo, double hi, double tol, int max_iters, double* state,
                   double* s_keypoint, int32_t* n_active, hipStream_t st);
+// one-step-ahead prediction errors and the exact log-likelihood (eks_innov.hip: scalar chains, on eks_em.hip's
+// summarize / scan and workspace; eks_dense.hip: general models, always the generic kernels)
+int diag_innovations(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, float* innov,
+                     float* innov_var, double* loglik, void* ws, size_t ws_bytes, hipStream_t st);
+size_t dense_innovations_workspace_bytes(int T, int K, int D, int O);
+int dense_innovations(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, float* innov,
+                      float* innov_var, float* nis, float* frame_ll, double* loglik, void* ws, size_t ws_bytes,
+                      hipStream_t st);
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M,
                  float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);

@@ -258,6 +258,32 @@ def em_stats(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False):
     return Sw
 
 
+INNOVATION_OUTPUTS = ('innov', 'innov_var', 'nis', 'frame_ll', 'loglik')
+
+
+def innovations(y, var, m0, S0, A, C, Q, s, flags: int = 0, want=INNOVATION_OUTPUTS):
+    """eks_innovations: the forward filter's prediction errors of the model eks_smooth runs.  Returns a dict of device
+    tensors with the outputs named in `want`: innov, innov_var (T, K, O) float32; nis, frame_ll (T, K) float32 (general
+    models only: on scalar chains, FLAG_DIAG_MODEL, the library refuses them); loglik float64, (K, D) per chain on
+    scalar chains and (K,) on general models."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
+    s = _chk(s, torch.float64, 's', (K,))
+    want = tuple(want)
+    if not want or any(w not in INNOVATION_OUTPUTS for w in want):
+        raise ValueError(f'want must name at least one of {INNOVATION_OUTPUTS}')
+    dims = _dims(K, T, D, O, flags)
+    shapes = dict(innov=(T, K, O), innov_var=(T, K, O), nis=(T, K), frame_ll=(T, K),
+                  loglik=(K, D) if flags & FLAG_DIAG_MODEL else (K,))
+    out = {n: torch.empty(shapes[n], dtype=torch.float64 if n == 'loglik' else torch.float32, device=y.device)
+           for n in INNOVATION_OUTPUTS if n in want}
+    ws = _workspace(lib.eks_innovations_workspace_bytes(ctypes.byref(dims)), y.device)
+    rc = lib.eks_innovations(ctypes.byref(dims), *[_ptr(b) for b in bufs], _ptr(s),
+                             *(_ptr(out.get(n)) for n in INNOVATION_OUTPUTS), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, 'eks_innovations')
+    return out
+
+
 class EmScaleLoop:
     """eks_em_scale_run with every buffer allocated once: `run(n)` enqueues n iterations of E-step + M-step for the
     scale without touching the host.  state (n_blocks, 4) float64 = {log s, last |delta log s|, iterations, done};

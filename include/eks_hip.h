@@ -179,6 +179,39 @@ int eks_em_scale_run(const eks_dims_t* dims, const float* y, const float* var, c
                      int32_t max_iters, int32_t n_iters, double* state, double* s_keypoint, double* Sw,
                      int32_t* n_active, void* workspace, size_t workspace_bytes, eks_stream_t stream);
 
+/* ---- the forward filter's view of the model eks_smooth runs (time-varying R = diag(clip(var_t, 1e-12, 1e30))): the
+ * prediction-error decomposition.  No reference counterpart: eks_nll has a constant R, eks_ar1_nll is the pupil
+ * smoother's loss.  dims, flags, inputs and the variance clip are those of eks_smooth; EKS_FLAG_VS_DIAG is ignored.
+ * Per frame t, from the PREDICTED belief (m_{t|t-1}, P_{t|t-1}) - the prior (m0, S0) at t = 0 - before any update
+ * with frame t:
+ *   innov     float32 [T][K][O]   v_t = y_t - C m_{t|t-1}
+ *   innov_var float32 [T][K][O]   the diagonal of S_t = C P_{t|t-1} C' + R_t
+ *   nis       float32 [T][K]      v' S^-1 v                                        (general models only)
+ *   frame_ll  float32 [T][K]      -0.5 (O log 2 pi + log det S_t + nis)            (general models only)
+ *   loglik    float64             the sum over frames: [K][D], per chain as Sw is, on scalar chains; [K] on general
+ *                                 models.  By Fisher's identity its derivative in log s is eks_em_stats' statistic.
+ * Every output may be NULL, not all of them (EKS_ERR_NULL); a NULL output costs no stores (and, for loglik, no
+ * logarithms).  Standardised innovations v / sqrt(innov_var) are N(0, 1) and white when the model is right.
+ *   scalar chains (EKS_FLAG_DIAG_MODEL): eks_em_stats' summarize and grouped Kalman scan as they are, then a forward
+ *     replay (eks_amd/csrc/eks_innov.hip) that forms S and d with filter_step's own expressions - the belief carried
+ *     forward is bit for bit the smoother's; the frame's term log 2 pi + log S + d^2 / S in float32, the sum in float64.
+ *     nis and frame_ll are elementwise functions of innov and innov_var there: a non-NULL pointer is
+ *     EKS_ERR_UNSUPPORTED.  y and var are read twice; with loglik alone nothing of length T is written.
+ *   general models: D <= 6 and O <= 64 (else EKS_ERR_UNSUPPORTED); the generic summarize / scan kernels of eks_smooth,
+ *     then a forward replay in float64 that rounds once (eks_amd/csrc/eks_dense.hip: dense_innovations): log det S_t
+ *     and nis from the sequential scalar updates, exact for the diagonal R; nothing is factored, so a singular Q or
+ *     S0 is fine while the innovation variances are positive.
+ * loglik is summed in float64 from one partial per (chunk, chain or keypoint) in a fixed order without floating-point
+ * atomics: two calls give the same bits, and on scalar chains a call on a subset of the keypoints gives that subset's
+ * bits.  T == 1 is valid.  A shape whose launches would index threads beyond an int is EKS_ERR_SHAPE, a small
+ * workspace EKS_ERR_WORKSPACE.  Every refusal is returned before anything is enqueued, the outputs stay untouched,
+ * and the workspace query returns 0 for refused shapes. ---------------------------------------------------------- */
+size_t eks_innovations_workspace_bytes(const eks_dims_t* dims);
+int eks_innovations(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,
+                    const double* A, const double* C, const double* Q, const double* s, float* innov,
+                    float* innov_var, float* nis, float* frame_ll, double* loglik, void* workspace,
+                    size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- constant observation noise for the loss: eks/core.py:702-709
  * rconst[k][o] = max(nanmedian_t max(var[t][k][o], 1e-12), min_var)  (float64 out) ----------- */
 size_t eks_const_r_workspace_bytes(const eks_dims_t* dims);
