@@ -29,6 +29,11 @@
 // against 20 us for the three launches, 50 000 x 30: 187 against 29 - see
 // profiles/r02_overlap_probes.txt.  Dropped.)
 //
+// From 32 768 frames on the fused form drops K1 and the scan (windowed replay, kWinG below): a K3 block reads two
+// more chunks on either side of its own and starts from a stand-in belief and zero information wherever the filter
+// has forgotten across those 64 frames (composed |A| <= 2^-30, checked per lane); a small probe launch in front and
+// the three launches above behind it, gated on a fail plane, replay the other lanes exactly.
+//
 // HBM traffic: 2 x (y + var) in, 1 x (ms + Vs) out (+ ~4 % for the chunk elements); no filtered
 // state ever touches memory.  No MFMA: the algebra is scalar.  No LDS in K1/K3: each datum is
 // consumed by the lane that loads it; lanes of a wave are consecutive chains, so every row access
@@ -302,6 +307,44 @@ struct BlockMap {
   int tile0;     // first tile of this launch (keypoint-tiled passes, diag_smooth)
 };
 
+// Windowed replay (T >= kWinMinT): a block replays kWinG consecutive chunks of a tile and reads kWinH more chunks on
+// either side instead of taking the belief entering it and the information leaving it from a scan of the whole
+// sequence.  Whatever lies beyond a run of frames reaches the far side only through the run's composed A
+// (elem_apply: A inv (m + P eta), A^2 inv P; elem_back likewise), so where |A| of the halo is at most kWinTol = 2^-30
+// a stand-in belief / zero information in front of the halo changes the entry state by less than 2^-30 of the local
+// spread - 1/60 of a float32 ulp.  Lanes whose halo does not forget that much store nothing and are replayed by the
+// gated exact launches that follow (DESIGN.md section 11 has the derivation and the measurements).
+// Geometry, measured on the MI355X (hip_ops.smooth alone, 100 000 frames x 512 chains, s from the 64-candidate grid,
+// same box, EKS_SMOOTH_WINDOW = 0 / 1; tools/smooth_window_time.py):
+//   G = 12, H = 2 (1 024 threads, 1.33 x the rows): the block's 16 waves cap the kernel at 128 VGPRs and it spills
+//                 (88-132 bytes of scratch per lane over the 18 forms): 260.2 -> 263.8 us, no gain;
+//   G =  8, H = 2 (  768 threads, 1.5 x the rows):  150-154 VGPRs, no scratch, one block per CU: 254.9 -> 233.5 us.
+// -DEKS_WIN_G=12 rebuilds the first for A/B.
+#ifndef EKS_WIN_G
+#define EKS_WIN_G 8
+#endif
+constexpr int kWinG = EKS_WIN_G;           // own chunks of a block
+constexpr int kWinH = 2;                   // halo chunks on either side (64 frames)
+constexpr int kWinW = kWinG + 2 * kWinH;   // waves of a block
+constexpr float kWinTol = 0x1p-30f;
+constexpr int kWinDefault = 1;             // EKS_SMOOTH_WINDOW when unset
+// Shortest sequence that takes the windowed form (EKS_SMOOTH_WINDOW_MIN_T).  128 chains, scan-based -> windowed:
+// 16 384 frames 20.2 -> 24.1 us, 32 768 frames 30.3 -> 30.5 us, 65 536 frames 50.3 -> 47.4 us; 32 768 is also the
+// largest value that keeps 40 000- and 50 000-frame sessions on one side of it.
+constexpr int kWinMinT = 32768;
+constexpr int kProbeWin = 8;               // the probe's windows per chain
+constexpr int kProbeLen = 64;              // frames of each
+static_assert(kWinG % kFW == 0, "the four chunks of an exact-replay block belong to one window group");
+static_assert(kWinG >= kWinH, "only the first window group's halo is cut by frame 0");
+
+struct WinWs {
+  unsigned char* slow;   // [N]       probe: some window of the chain does not forget (null: nobody is slow)
+  unsigned char* fail;   // [nwg][N]  windowed replay: this (window group, chain) was not stored (null: test mode)
+  int* gate;             // [tiles]   some lane of the tile needs the exact launches
+  int nwg;               // window groups = ceil(nc / kWinG)
+  int nan_bad;           // test mode: lanes that fail the check store NaN, nothing is recorded
+};
+
 // Row access of the fused kernels through buffer resources based at the first row of the wave's
 // chunk and tile (scalar): `buffer_load_dword v, v_lane, s[rsrc], s_row offen` - the row offset is
 // an SGPR, the lane offset a constant VGPR, so loads and stores cost no VALU address arithmetic
@@ -354,9 +397,12 @@ template <int B, bool UNIT, bool RC>
 __global__ __launch_bounds__(64 * kFW) void diag_summarize_blk_kernel(BlockMap L, DiagModel M, DiagWs W,
                                                                      ScanWs S,
                                                                      const float* __restrict__ y,
-                                                                     const float* __restrict__ var) {
+                                                                     const float* __restrict__ var,
+                                                                     const int* __restrict__ gate) {
   __shared__ float sh[5][kFW][64];
   __shared__ int arrived;
+  // exact fallback behind the windowed replay: nothing to do unless some lane of the tile failed (block-uniform)
+  if (gate && gate[L.tile0 + blockIdx.x % L.ntile] == 0) return;
   // the wave index through readfirstlane: chunk, first frame and length are then scalars to the
   // compiler (row addresses in SGPRs, the tail test a scalar branch)
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -416,19 +462,13 @@ __global__ __launch_bounds__(64 * kFW) void diag_summarize_blk_kernel(BlockMap L
   S.gJ[o] = a.J;
 }
 
-// K3f: replay of chunk j = grp * kFW + w.  The belief entering the block and the information
-// leaving it come from the scan of the block aggregates; the wave pushes the former through the
-// elements of the chunks before its own and pulls the latter back through those after it (<= 7
-// compositions each, element rows shared by the block's waves through L2) before it streams its
-// own 64 rows of y, var (holding both sets of elements in registers beside the chunk cost 180 VGPRs
-// and two thirds of the occupancy).
-template <int B, bool UNIT, int VS_ROW, bool RC>
-__global__ __launch_bounds__(64 * kFW) void diag_replay_blk_kernel(BlockMap L, DiagModel M, DiagWs W,
-                                                                  ScanWs S,
-                                                                  const float* __restrict__ y,
-                                                                  const float* __restrict__ var,
-                                                                  float* __restrict__ ms,
-                                                                  float* __restrict__ Vs) {
+// Recompute form of K3f (described below): shared by diag_replay_blk_kernel and, MASKED, by the gated exact launch that follows
+// the windowed replay.
+template <int B, bool UNIT, int VS_ROW, bool MASKED>
+__device__ __forceinline__ void replay_recompute_block(const BlockMap& L, const DiagModel& M, const ScanWs& S,
+                                                       const WinWs& Wn, const float* __restrict__ y,
+                                                       const float* __restrict__ var, float* __restrict__ ms,
+                                                       float* __restrict__ Vs) {
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int tile = L.tile0 + blockIdx.x % L.ntile;
   int grp = blockIdx.x / L.ntile;
@@ -436,7 +476,183 @@ __global__ __launch_bounds__(64 * kFW) void diag_replay_blk_kernel(BlockMap L, D
   const int n = tile * 64 + lane, j = grp * kFW + w;
   const int j0 = grp * kFW, j1 = min(j0 + kFW, L.nc);
   constexpr int VW = VS_ROW == 0 ? 1 : VS_ROW;
-  if constexpr (!RC) {
+  // K1 kept no chunk elements: every wave summarises its own chunk again from the rows it has just
+  // loaded (15 VALU instructions per frame) and the block's waves exchange the elements through
+  // LDS, read where they are used - no neighbour-element registers (124 VGPRs, 4 waves per SIMD).
+  __shared__ float sh[5][kFW][64];
+  bool keep = true;
+  if constexpr (MASKED) {
+    // exact fallback behind the windowed replay: only the lanes it did not store (slow by the probe, or failed the
+    // check in this chunk's window group).  The waves of a block hold the same chains and kFW divides kWinG, so the
+    // early return is block-uniform and comes before the barrier.
+    if (Wn.gate[tile] == 0) return;
+    keep = n < L.N && (Wn.slow[n] | Wn.fail[(size_t)(j0 / kWinG) * L.N + n]) != 0;
+    if (__ballot(keep) == 0) return;
+  }
+  const bool live = n < L.N && j < L.nc;   // every wave reaches the block's barrier
+  ChainParams<float> p{1.f, 1.f, 0.f};
+  const int t0 = j < L.nc ? j * B : 0;
+  const int len = j < L.nc ? min(B, L.T - t0) : 0;
+  const bool full = len == B;
+  const size_t first = (size_t)t0 * L.N + (size_t)tile * 64;
+  const BufferRows rows{rows_rsrc(y + first), rows_rsrc(var + first), (unsigned)lane * 4, (unsigned)L.N * 4};
+  float v0[B], v1[B];
+  Elem<float> own = elem_identity<float>();
+  if (live) {
+    p = load_chain_params(M, n);
+    if (full) {
+      load_rows<B, true>(rows, B, v0, v1);
+      own = summarize_loaded<B, UNIT, true>(v0, v1, B, p);
+    } else {
+      load_rows<B, false>(rows, len, v0, v1);
+      own = summarize_loaded<B, UNIT, false>(v0, v1, len, p);
+    }
+  }
+  sh[0][w][lane] = own.A; sh[1][w][lane] = own.b; sh[2][w][lane] = own.C; sh[3][w][lane] = own.eta;
+  sh[4][w][lane] = own.J;
+  __syncthreads();
+  if (!live) return;
+  auto lds_elem = [&](int q) {
+    return Elem<float>{sh[0][q][lane], sh[1][q][lane], sh[2][q][lane], sh[3][q][lane], sh[4][q][lane]};
+  };
+  const size_t ob = (size_t)grp * L.N + n;
+  float m = S.bm[ob], P = S.bP[ob], eta = S.bEta[ob], J = S.bJ[ob];
+#pragma unroll
+  for (int q = 0; q < kFW - 1; ++q)
+    if (q < w) elem_apply(lds_elem(q), m, P);
+  Elem<float> eb[kFW - 1];
+#pragma unroll
+  for (int q = 0; q < kFW - 1; ++q)
+    if (j + 1 + q < j1) eb[q] = lds_elem(w + 1 + q);
+  if (full) filter_loaded<B, UNIT, true>(v0, v1, B, p, m, P);
+  else filter_loaded<B, UNIT, false>(v0, v1, len, p, m, P);
+#pragma unroll
+  for (int q = kFW - 2; q >= 0; --q)
+    if (j + 1 + q < j1) elem_back(eb[q], eta, J);
+  fuse_info(m, P, eta, J);
+  const BufferStore<VS_ROW> st{rows_rsrc(ms + first), rows_rsrc(Vs + first * VW), (unsigned)lane * 4,
+                               (unsigned)L.N * 4, n % M.D};
+  if (!MASKED || keep) {
+    if (full) smooth_rows<B, UNIT, true>(v0, v1, B, p, m, P, st);
+    else smooth_rows<B, UNIT, false>(v0, v1, len, p, m, P, st);
+  }
+}
+
+// Windowed form of K3f: block = (64-chain tile, window group of kWinG chunks), kWinW waves.  Every wave loads and
+// summarises its chunk as the recompute form does; the halo waves retire after the exchange, the own waves compose the
+// halo in front of the group onto a stand-in belief and zero information back through the halo behind it.  Nothing
+// here waits for another block or reads what another kernel left.
+template <int B, bool UNIT, int VS_ROW>
+__device__ __forceinline__ void replay_window_block(const BlockMap& L, const DiagModel& M, const WinWs& Wn,
+                                                    const float* __restrict__ y, const float* __restrict__ var,
+                                                    float* __restrict__ ms, float* __restrict__ Vs) {
+  __shared__ float sh[5][kWinW][64];
+  __shared__ float shy[64];                  // the chains' observations on the halo's first frame
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int tile = L.tile0 + blockIdx.x % L.ntile;
+  int wg = blockIdx.x / L.ntile;
+  if (L.reverse) wg = Wn.nwg - 1 - wg;
+  const int n = tile * 64 + lane;
+  constexpr int VW = VS_ROW == 0 ? 1 : VS_ROW;
+  const bool slow = n >= L.N || (Wn.slow != nullptr && Wn.slow[n] != 0);
+  if (__ballot(!slow) == 0) return;          // all 64 chains are the exact launches': no row is requested (block-uniform)
+  const int jh0 = wg * kWinG - kWinH;        // first chunk of the halo in front (negative: cut by frame 0)
+  const int j = jh0 + w;
+  const bool valid = j >= 0 && j < L.nc;
+  const bool live = n < L.N && valid;
+  ChainParams<float> p{1.f, 1.f, 0.f};
+  const int t0 = valid ? j * B : 0;
+  const int len = valid ? min(B, L.T - t0) : 0;
+  const bool full = len == B;
+  const size_t first = (size_t)t0 * L.N + (size_t)tile * 64;
+  const BufferRows rows{rows_rsrc(y + first), rows_rsrc(var + first), (unsigned)lane * 4, (unsigned)L.N * 4};
+  float v0[B], v1[B];
+  Elem<float> own = elem_identity<float>();   // chunks outside the sequence compose as identities
+  float y0 = 0.f;
+  if (live) {
+    p = load_chain_params(M, n);
+    if (full) {
+      load_rows<B, true>(rows, B, v0, v1);
+      y0 = v0[0];
+      own = summarize_loaded<B, UNIT, true>(v0, v1, B, p);
+    } else {
+      load_rows<B, false>(rows, len, v0, v1);
+      y0 = v0[0];
+      own = summarize_loaded<B, UNIT, false>(v0, v1, len, p);
+    }
+  }
+  sh[0][w][lane] = own.A; sh[1][w][lane] = own.b; sh[2][w][lane] = own.C; sh[3][w][lane] = own.eta;
+  sh[4][w][lane] = own.J;
+  if (w == 0) shy[lane] = y0;
+  __syncthreads();
+  const int wo = w - kWinH;                  // own chunk within the group
+  if (wo < 0 || wo >= kWinG || !live) return;
+  auto lds_elem = [&](int q) {
+    return Elem<float>{sh[0][q][lane], sh[1][q][lane], sh[2][q][lane], sh[3][q][lane], sh[4][q][lane]};
+  };
+  // a halo that reaches frame 0 starts from the chain's prior, one that reaches the last frame ends with no
+  // information: both exact, no check
+  const bool cut_front = jh0 <= 0, cut_back = (wg + 1) * kWinG + kWinH >= L.nc;
+  Elem<float> hf = lds_elem(0), hb = lds_elem(kWinH + kWinG);
+#pragma unroll
+  for (int q = 1; q < kWinH; ++q) {
+    hf = elem_combine(hf, lds_elem(q));
+    hb = elem_combine(hb, lds_elem(kWinH + kWinG + q));
+  }
+  float m, P;
+  load_chain_prior(M, n, m, P);
+  if (!cut_front) m = UNIT ? shy[lane] : shy[lane] * rcp(p.c);   // stand-in: what the halo's first frame saw, variance S0
+  // (comparisons written so that NaN fails)
+  const bool good = !slow && fabsf(m) <= 3e38f && (cut_front || fabsf(hf.A) <= kWinTol) &&
+                    (cut_back || fabsf(hb.A) <= kWinTol);
+  if (!good && !slow && wo == 0 && Wn.fail != nullptr) {
+    Wn.fail[(size_t)wg * L.N + n] = 1;
+    atomicOr(&Wn.gate[tile], 1);
+  }
+  elem_apply(hf, m, P);
+  for (int q = 0; q < wo; ++q) elem_apply(lds_elem(kWinH + q), m, P);
+  if (full) filter_loaded<B, UNIT, true>(v0, v1, B, p, m, P);
+  else filter_loaded<B, UNIT, false>(v0, v1, len, p, m, P);
+  float eta = 0.f, J = 0.f;
+  elem_back(hb, eta, J);
+  for (int q = kWinG - 1; q > wo; --q) elem_back(lds_elem(kWinH + q), eta, J);
+  fuse_info(m, P, eta, J);
+  if (Wn.nan_bad && !good) m = P = __builtin_nanf("");
+  const BufferStore<VS_ROW> st{rows_rsrc(ms + first), rows_rsrc(Vs + first * VW), (unsigned)lane * 4,
+                               (unsigned)L.N * 4, n % M.D};
+  if (good || Wn.nan_bad) {
+    if (full) smooth_rows<B, UNIT, true>(v0, v1, B, p, m, P, st);
+    else smooth_rows<B, UNIT, false>(v0, v1, len, p, m, P, st);
+  }
+}
+
+// K3 forms of the fused path
+constexpr int kFormElems = 0;      // chunk elements and per-group scan results from K1 / the group scan
+constexpr int kFormRecompute = 1;  // the same, every chunk summarised again in K3
+constexpr int kFormWindow = 2;     // no K1, no scan: halo chunks instead
+
+// K3f: replay of chunk j = grp * kFW + w.  The belief entering the block and the information
+// leaving it come from the scan of the block aggregates; the wave pushes the former through the
+// elements of the chunks before its own and pulls the latter back through those after it (<= 7
+// compositions each, element rows shared by the block's waves through L2) before it streams its
+// own 64 rows of y, var (holding both sets of elements in registers beside the chunk cost 180 VGPRs
+// and two thirds of the occupancy).
+template <int B, bool UNIT, int VS_ROW, int FORM>
+__global__ __launch_bounds__(FORM == kFormWindow ? 64 * kWinW : 64 * kFW) void diag_replay_blk_kernel(
+    BlockMap L, DiagModel M, DiagWs W, ScanWs S, WinWs Wn, const float* __restrict__ y, const float* __restrict__ var,
+    float* __restrict__ ms, float* __restrict__ Vs) {
+  if constexpr (FORM == kFormWindow) {
+    replay_window_block<B, UNIT, VS_ROW>(L, M, Wn, y, var, ms, Vs);
+  } else if constexpr (FORM == kFormRecompute) {
+    replay_recompute_block<B, UNIT, VS_ROW, false>(L, M, S, Wn, y, var, ms, Vs);
+  } else {
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int tile = L.tile0 + blockIdx.x % L.ntile;
+    int grp = blockIdx.x / L.ntile;
+    if (L.reverse) grp = L.ngrp - 1 - grp;
+    const int n = tile * 64 + lane, j = grp * kFW + w;
+    const int j0 = grp * kFW, j1 = min(j0 + kFW, L.nc);
+    constexpr int VW = VS_ROW == 0 ? 1 : VS_ROW;
     if (n >= L.N || j >= L.nc) return;
     // everything the forward pass needs is requested at once: the chunk's own 64 rows, then the
     // elements of the block's earlier chunks (wave-uniform predicate)
@@ -473,57 +689,61 @@ __global__ __launch_bounds__(64 * kFW) void diag_replay_blk_kernel(BlockMap L, D
                                  (unsigned)L.N * 4, n % M.D};
     if (full) smooth_rows<B, UNIT, true>(v0, v1, B, p, m, P, st);
     else smooth_rows<B, UNIT, false>(v0, v1, len, p, m, P, st);
-  } else {
-    // K1 kept no chunk elements: every wave summarises its own chunk again from the rows it has just
-    // loaded (15 VALU instructions per frame) and the block's waves exchange the elements through
-    // LDS, read where they are used - no neighbour-element registers (124 VGPRs, 4 waves per SIMD).
-    __shared__ float sh[5][kFW][64];
-    const bool live = n < L.N && j < L.nc;   // every wave reaches the block's barrier
-    ChainParams<float> p{1.f, 1.f, 0.f};
-    const int t0 = j < L.nc ? j * B : 0;
-    const int len = j < L.nc ? min(B, L.T - t0) : 0;
-    const bool full = len == B;
-    const size_t first = (size_t)t0 * L.N + (size_t)tile * 64;
-    const BufferRows rows{rows_rsrc(y + first), rows_rsrc(var + first), (unsigned)lane * 4, (unsigned)L.N * 4};
-    float v0[B], v1[B];
-    Elem<float> own = elem_identity<float>();
-    if (live) {
-      p = load_chain_params(M, n);
-      if (full) {
-        load_rows<B, true>(rows, B, v0, v1);
-        own = summarize_loaded<B, UNIT, true>(v0, v1, B, p);
-      } else {
-        load_rows<B, false>(rows, len, v0, v1);
-        own = summarize_loaded<B, UNIT, false>(v0, v1, len, p);
-      }
-    }
-    sh[0][w][lane] = own.A; sh[1][w][lane] = own.b; sh[2][w][lane] = own.C; sh[3][w][lane] = own.eta;
-    sh[4][w][lane] = own.J;
-    __syncthreads();
-    if (!live) return;
-    auto lds_elem = [&](int q) {
-      return Elem<float>{sh[0][q][lane], sh[1][q][lane], sh[2][q][lane], sh[3][q][lane], sh[4][q][lane]};
-    };
-    const size_t ob = (size_t)grp * L.N + n;
-    float m = S.bm[ob], P = S.bP[ob], eta = S.bEta[ob], J = S.bJ[ob];
-#pragma unroll
-    for (int q = 0; q < kFW - 1; ++q)
-      if (q < w) elem_apply(lds_elem(q), m, P);
-    Elem<float> eb[kFW - 1];
-#pragma unroll
-    for (int q = 0; q < kFW - 1; ++q)
-      if (j + 1 + q < j1) eb[q] = lds_elem(w + 1 + q);
-    if (full) filter_loaded<B, UNIT, true>(v0, v1, B, p, m, P);
-    else filter_loaded<B, UNIT, false>(v0, v1, len, p, m, P);
-#pragma unroll
-    for (int q = kFW - 2; q >= 0; --q)
-      if (j + 1 + q < j1) elem_back(eb[q], eta, J);
-    fuse_info(m, P, eta, J);
-    const BufferStore<VS_ROW> st{rows_rsrc(ms + first), rows_rsrc(Vs + first * VW), (unsigned)lane * 4,
-                                 (unsigned)L.N * 4, n % M.D};
-    if (full) smooth_rows<B, UNIT, true>(v0, v1, B, p, m, P, st);
-    else smooth_rows<B, UNIT, false>(v0, v1, len, p, m, P, st);
   }
+}
+
+// The exact replay behind the windowed one: the recompute form for the lanes marked in the fail plane or slow by the
+// probe, nothing for the rest.
+template <int B, bool UNIT, int VS_ROW>
+__global__ __launch_bounds__(64 * kFW) void diag_replay_exact_kernel(BlockMap L, DiagModel M, ScanWs S, WinWs Wn,
+                                                                    const float* __restrict__ y,
+                                                                    const float* __restrict__ var,
+                                                                    float* __restrict__ ms,
+                                                                    float* __restrict__ Vs) {
+  replay_recompute_block<B, UNIT, VS_ROW, true>(L, M, S, Wn, y, var, ms, Vs);
+}
+
+// Ahead of the windowed replay: block = one 64-chain tile x kProbeWin windows of kProbeLen frames (first frames a
+// function of T alone).  A chain is slow when the composed A of any window - the product of a (1 - K_t c) of a filter
+// started from certainty, which needs the variances only - exceeds kWinTol.  Only a classifier (the replay's own check
+// decides what is stored): it keeps a session whose chosen s is small from paying the windowed pass before the exact
+// one.  Also clears the tile's columns of the fail plane and sets its gate.
+__global__ __launch_bounds__(64 * kProbeWin) void diag_window_probe_kernel(int N, int T, DiagModel M, WinWs Wn,
+                                                                          const float* __restrict__ var,
+                                                                          int classify) {
+  __shared__ int bad[kProbeWin][64];
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int tile = blockIdx.x, n = tile * 64 + lane;
+  for (int i = threadIdx.x; i < Wn.nwg * 64; i += 64 * kProbeWin) {
+    const int c = tile * 64 + (i & 63);
+    if (c < N) Wn.fail[(size_t)(i >> 6) * N + c] = 0;
+  }
+  int s = 0;
+  if (classify && n < N) {
+    const ChainParams<float> p = load_chain_params(M, n);
+    const int t0 = (int)((long long)w * (T - kProbeLen) / (kProbeWin - 1));
+    const float* v = var + (size_t)t0 * N + n;
+    float r[kProbeLen];
+#pragma unroll
+    for (int i = 0; i < kProbeLen; ++i) r[i] = v[(size_t)i * N];
+    float A = 1.f, C = 0.f;
+#pragma unroll
+    for (int i = 0; i < kProbeLen; ++i) {
+      const float ri = clip_var(r[i]);
+      const float rg = ri * rcp(ri + C * p.c * p.c);
+      A = p.times_a(A * rg);
+      C = p.times_a2(C * rg) + p.q_s;
+    }
+    s = !(fabsf(A) <= kWinTol);              // NaN is slow
+  }
+  bad[w][lane] = s;
+  __syncthreads();
+  if (w != 0) return;
+#pragma unroll
+  for (int q = 1; q < kProbeWin; ++q) s |= bad[q][lane];
+  if (n < N) Wn.slow[n] = (unsigned char)s;
+  const bool any = __ballot(s != 0) != 0;
+  if (lane == 0) Wn.gate[tile] = any ? 1 : 0;
 }
 
 // S2f: scan of the block aggregates, ngrp per chain (hundreds to thousands).  Block = CH chains x
@@ -535,9 +755,12 @@ __global__ __launch_bounds__(64 * kFW) void diag_replay_blk_kernel(BlockMap L, D
 // slot walks its aggregates again from the belief entering its first one (forward) / the
 // information leaving its last one (backward), writing the per-block results.
 template <int PER, int CH>
-__global__ __launch_bounds__(64 * CH) void diag_scan_groups_kernel(int N, int n0, int n1, DiagModel M, ScanWs S) {
+__global__ __launch_bounds__(64 * CH) void diag_scan_groups_kernel(int N, int n0, int n1, DiagModel M, ScanWs S,
+                                                                  const int* __restrict__ gate) {
   constexpr int NW = CH;                   // waves per block (64 slots x CH chains / 64 lanes)
   __shared__ float tot[2][5][NW][CH];      // [direction][field][wave][chain]
+  static_assert(64 % CH == 0, "a block's chains lie in one 64-chain tile (n0 is a multiple of 64)");
+  if (gate && gate[(n0 + xcd_contiguous_block(blockIdx.x, gridDim.x) * CH) >> 6] == 0) return;   // block-uniform
   const int c = threadIdx.x % CH, slot = threadIdx.x / CH, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // Workgroups are dealt to the 8 XCDs round-robin and each XCD has its own L2: with CH = 4 the 16-byte pieces
   // of one 64-byte line belong to four consecutive blocks, i.e. to four different L2s, and the launch fetched
@@ -640,10 +863,17 @@ constexpr int kChunk = EKS_DIAG_CHUNK;  // frames per lane; 2*B VGPRs hold the c
 
 static inline size_t plane_bytes(int nc, int N) { return align_up((size_t)nc * N * sizeof(float), 256); }
 
+// the windowed replay's byte planes and gate words, behind the float planes: slow [N], fail [nwg][N], gate [tiles]
+static inline size_t win_slow_bytes(int N) { return align_up((size_t)N, 256); }
+static inline size_t win_fail_bytes(int nc, int N) { return align_up((size_t)((nc + kWinG - 1) / kWinG) * N, 256); }
+static inline size_t win_bytes(int nc, int N) {
+  return win_slow_bytes(N) + win_fail_bytes(nc, N) + align_up((size_t)((N + 63) / 64) * sizeof(int), 256);
+}
+
 size_t diag_smooth_workspace_bytes(int T, int N) {
   const int nc = (T + kChunk - 1) / kChunk;
   const int nblk = (nc + kFW - 1) / kFW;       // fused grouping (>= the legacy nc / kScanCB blocks)
-  return 9 * plane_bytes(nc, N) + 9 * plane_bytes(nblk, N);
+  return 9 * plane_bytes(nc, N) + 9 * plane_bytes(nblk, N) + win_bytes(nc, N);
 }
 
 static LaneMap make_lane_map(int T, int N, int B) {
@@ -717,6 +947,26 @@ int diag_smooth(const eks_dims_t& d, const float* y, const float* var, const Dia
   // picks which of the two runs backwards (A/B knob).
   const int k1_reverse = knob_int(KNOB_SUMMARIZE_REVERSE, 0) == 1 ? 1 : 0;
   const int k3_reverse = knob_set(KNOB_REPLAY_FORWARD) ? (knob_int(KNOB_REPLAY_FORWARD, 0) == 1 ? 0 : 1) : !k1_reverse;
+  // Windowed replay where the fused form is taken and the sequence is long enough - by T alone: which arithmetic a
+  // (chain, window group) gets is a function of that chain's data and T only (probe, check, group boundaries), so a
+  // keypoint subset run on its own reproduces its slice of a wider run bit for bit (tests/test_gpu_large.py).
+  // EKS_SMOOTH_WINDOW: 0 the path below alone, 1 windowed + probe + gated exact launches, 2 test mode (no probe, no
+  // exact launches, failing lanes store NaN).
+  const int win_mode = knob_int(KNOB_SMOOTH_WINDOW, kWinDefault);
+  const int win_min_t = max(kProbeLen, knob_int(KNOB_SMOOTH_WINDOW_MIN_T, kWinMinT));
+  const bool windowed = fused && win_mode != 0 && T >= win_min_t;
+  WinWs Wn{nullptr, nullptr, nullptr, (L.nc + kWinG - 1) / kWinG, 0};
+  if (windowed) {
+    char* wb = base + 9 * pb + 9 * sb;
+    if (win_mode == 2) {
+      Wn.nan_bad = 1;
+    } else {
+      Wn.slow = reinterpret_cast<unsigned char*>(wb);
+      Wn.fail = reinterpret_cast<unsigned char*>(wb + win_slow_bytes(N));
+      Wn.gate = reinterpret_cast<int*>(wb + win_slow_bytes(N) + win_fail_bytes(L.nc, N));
+    }
+  }
+  const int* gate = windowed ? Wn.gate : nullptr;
   if (fused) {
     // (keypoint-tiled passes - the three launches per group of 64-chain tiles, so that a pass's rows are still in the
     //  Infinity Cache when its K3 asks for them - were built and measured in round 3: 264 -> 290-425 us on C3, K3 is no
@@ -736,25 +986,63 @@ int diag_smooth(const eks_dims_t& d, const float* y, const float* var, const Dia
     // 0.64 -> 0.56 ms, K3 1.37 -> 1.33 ms, step 2.06 -> 1.94 ms; C3 (512 chains, 32 MB) K1 83 -> 75 us,
     // K3 168 -> 165 us, step 0.597 -> 0.591 ms; C2 (128 chains, 0.8 MB) K3 8.9 -> 13.3 us - one more
     // dependent pass in a latency-bound launch.  Hence the threshold on the element bytes.
-    const bool rc = rc_all;
+    const bool rc = rc_all || windowed;      // (the exact launches behind the windowed replay keep no elements)
 #define EKS_K1_BLK(UN)                                                                                  \
   do {                                                                                                  \
     if (rc)                                                                                             \
       hipLaunchKernelGGL((diag_summarize_blk_kernel<kChunk, UN, true>), bgrid, bblock, 0, st, Bm, M, W, \
-                         S, y, var);                                                                    \
+                         S, y, var, gate);                                                              \
     else                                                                                                \
       hipLaunchKernelGGL((diag_summarize_blk_kernel<kChunk, UN, false>), bgrid, bblock, 0, st, Bm, M,   \
-                         W, S, y, var);                                                                 \
+                         W, S, y, var, gate);                                                           \
   } while (0)
 #define EKS_K3_BLK(UN, R)                                                                               \
   do {                                                                                                  \
-    if (rc)                                                                                             \
-      hipLaunchKernelGGL((diag_replay_blk_kernel<kChunk, UN, R, true>), bgrid, bblock, 0, st, Bm, M, W, \
-                         S, y, var, ms, Vs);                                                            \
+    if (windowed)                                                                                       \
+      hipLaunchKernelGGL((diag_replay_exact_kernel<kChunk, UN, R>), bgrid, bblock, 0, st, Bm, M, S, Wn, \
+                         y, var, ms, Vs);                                                               \
+    else if (rc)                                                                                        \
+      hipLaunchKernelGGL((diag_replay_blk_kernel<kChunk, UN, R, kFormRecompute>), bgrid, bblock, 0, st, \
+                         Bm, M, W, S, Wn, y, var, ms, Vs);                                              \
     else                                                                                                \
-      hipLaunchKernelGGL((diag_replay_blk_kernel<kChunk, UN, R, false>), bgrid, bblock, 0, st, Bm, M,   \
-                         W, S, y, var, ms, Vs);                                                         \
+      hipLaunchKernelGGL((diag_replay_blk_kernel<kChunk, UN, R, kFormElems>), bgrid, bblock, 0, st, Bm, \
+                         M, W, S, Wn, y, var, ms, Vs);                                                  \
   } while (0)
+#define EKS_K3_WIN(UN, R)                                                                               \
+  hipLaunchKernelGGL((diag_replay_blk_kernel<kChunk, UN, R, kFormWindow>), wgrid, dim3(64 * kWinW), 0,  \
+                     st, Bw, M, W, S, Wn, y, var, ms, Vs)
+#define EKS_REPLAY_WIN(R)                                                                              \
+  case R:                                                                                              \
+    if (unit)                                                                                          \
+      EKS_K3_WIN(true, R);                                                                             \
+    else                                                                                               \
+      EKS_K3_WIN(false, R);                                                                            \
+    break;
+    if (windowed) {
+      if (win_mode != 2) {
+        ProfScope ps("diag_window_probe", st);
+        hipLaunchKernelGGL(diag_window_probe_kernel, dim3(ntl), dim3(64 * kProbeWin), 0, st, N, T, M, Wn, var,
+                           knob_int(KNOB_SMOOTH_WINDOW_PROBE, 1) != 0 ? 1 : 0);
+      }
+      {
+        ProfScope ps("diag_replay", st);
+        BlockMap Bw = Bm;
+        Bw.reverse = k3_reverse;
+        const dim3 wgrid((unsigned)((long)Bw.ntile * Wn.nwg));
+        switch (vs_row) {
+          EKS_REPLAY_WIN(0)
+          EKS_REPLAY_WIN(1)
+          EKS_REPLAY_WIN(2)
+          EKS_REPLAY_WIN(3)
+          EKS_REPLAY_WIN(4)
+          EKS_REPLAY_WIN(5)
+          EKS_REPLAY_WIN(6)
+          EKS_REPLAY_WIN(7)
+          EKS_REPLAY_WIN(8)
+        }
+      }
+      if (win_mode == 2) continue;
+    }
     {
       ProfScope ps("diag_summarize", st);
       if (unit)
@@ -772,17 +1060,17 @@ int diag_smooth(const eks_dims_t& d, const float* y, const float* var, const Dia
       const int Ne = n0 + Np;                 // chains [n0, Ne) are scanned by this launch
       if (ch4) {
         if (per8)
-          hipLaunchKernelGGL((diag_scan_groups_kernel<8, 4>), dim3((Np + 3) / 4), dim3(256), 0, st, N, n0, Ne, M, S);
+          hipLaunchKernelGGL((diag_scan_groups_kernel<8, 4>), dim3((Np + 3) / 4), dim3(256), 0, st, N, n0, Ne, M, S, gate);
         else
-          hipLaunchKernelGGL((diag_scan_groups_kernel<16, 4>), dim3((Np + 3) / 4), dim3(256), 0, st, N, n0, Ne, M, S);
+          hipLaunchKernelGGL((diag_scan_groups_kernel<16, 4>), dim3((Np + 3) / 4), dim3(256), 0, st, N, n0, Ne, M, S, gate);
       } else {
         if (per8)
-          hipLaunchKernelGGL((diag_scan_groups_kernel<8, 16>), dim3((Np + 15) / 16), dim3(1024), 0, st, N, n0, Ne, M, S);
+          hipLaunchKernelGGL((diag_scan_groups_kernel<8, 16>), dim3((Np + 15) / 16), dim3(1024), 0, st, N, n0, Ne, M, S, gate);
         else
-          hipLaunchKernelGGL((diag_scan_groups_kernel<16, 16>), dim3((Np + 15) / 16), dim3(1024), 0, st, N, n0, Ne, M, S);
+          hipLaunchKernelGGL((diag_scan_groups_kernel<16, 16>), dim3((Np + 15) / 16), dim3(1024), 0, st, N, n0, Ne, M, S, gate);
       }
     }
-    ProfScope ps("diag_replay", st);
+    ProfScope ps(windowed ? "diag_replay_exact" : "diag_replay", st);
     Bm.reverse = k3_reverse;
 #define EKS_REPLAY_BLK(R)                                                                              \
   case R:                                                                                              \
@@ -804,6 +1092,8 @@ int diag_smooth(const eks_dims_t& d, const float* y, const float* var, const Dia
     }
     }  // passes
 #undef EKS_REPLAY_BLK
+#undef EKS_REPLAY_WIN
+#undef EKS_K3_WIN
 #undef EKS_K3_BLK
 #undef EKS_K1_BLK
     return hip_status(hipGetLastError());
