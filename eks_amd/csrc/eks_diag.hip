@@ -383,10 +383,25 @@ struct BufferStore {
       const u2 v = {__builtin_bit_cast(unsigned, d == 0 ? P : 0.0f), __builtin_bit_cast(unsigned, d == 1 ? P : 0.0f)};
       __builtin_amdgcn_raw_buffer_store_b64(v, rV, voff * 2, so * 2, kAuxNt);
     } else {
+      // Rows of three floats and more leave in pieces of 8 bytes (and one of 4), never as one 12- or 16-byte store.
+      // Written as W 4-byte stores they were merged into buffer_store_dwordx3 / x4 with the row offset in an SGPR, and
+      // in the windowed kernel the instruction behind such a store is the next frame's arithmetic writing the store's
+      // first data register: no wait state is inserted there, and on the MI355X the element in that register (row
+      // element 0, or 4 of an 8-wide row) left with the overwritten value on a few lanes per wave, differently from run
+      // to run (tests/test_gpu_smooth_window.py: every state width).  A store of at most 64 bits has no such window;
+      // the empty asm statements keep the pieces from being merged again.
+      typedef unsigned u2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-      for (unsigned e = 0; e < W; ++e)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (int)e == d ? P : 0.0f), rV,
-                                              voff * W + 4 * e, so * W, kAuxNt);
+      for (unsigned e = 0; e + 1 < W; e += 2) {
+        const u2 v = {__builtin_bit_cast(unsigned, (int)e == d ? P : 0.0f),
+                      __builtin_bit_cast(unsigned, (int)e + 1 == d ? P : 0.0f)};
+        __builtin_amdgcn_raw_buffer_store_b64(v, rV, voff * W + 4 * e, so * W, kAuxNt);
+        asm volatile("" ::: "memory");
+      }
+      if constexpr (W % 2 == 1)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (int)W - 1 == d ? P : 0.0f), rV,
+                                              voff * W + 4 * (W - 1), so * W, kAuxNt);
+      asm volatile("" ::: "memory");
     }
   }
 };

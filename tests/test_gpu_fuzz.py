@@ -23,6 +23,18 @@ def test_scalar_chain_kernels_random_shapes(seed):
     assert 'above 1e-5' not in out and "'med': 0.0" in out, out[-2000:]
 
 
+def test_smoother_random_shapes_in_the_windowed_form():
+    """The same draws of s over e^+-8, variance scales over e^+-4 and clipped zeros, at T >= 1024 with the windowed form
+    switched on from 1024 frames and D in {1, 2, 3}: windowed and scan-based against the oracle, and both kinds of lane
+    (stored by the windowed kernel, left to the exact launches) occur."""
+    import re
+    out = _run('fuzz_parity.py', 10, 909, 'window')
+    assert 'above 1e-5' not in out and 'worst' in out, out[-3000:]
+    stored, lanes = map(int, re.search(r'stored lanes (\d+) of (\d+)', out).groups())
+    assert 0 < stored < lanes, out[-3000:]
+    assert out.count('windowed ms') == 10, out[-3000:]
+
+
 def test_gradient_path_and_general_kernels_random_shapes():
     out = _run('fuzz_parity2.py', 18, 303)
     assert 'above 1e-5' not in out and 'worst' in out, out[-2000:]

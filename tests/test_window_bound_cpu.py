@@ -22,62 +22,8 @@ every smoothed mean of the group is within 2^-30 (front + back spread) / min(1, 
 variances."""
 import numpy as np
 
-B, H, G = 32, 2, 8                # frames per chunk, halo chunks per side, own chunks per window group
-TOL = 2.0 ** -30
-BAR = 2.0 ** -29
-
-
-def _identity(n):
-    return dict(A=np.ones(n), b=np.zeros(n), C=np.zeros(n), eta=np.zeros(n), J=np.zeros(n))
-
-
-def _append(e, y, r, a, c, q):
-    g = 1.0 / (r + e['C'] * c * c)
-    d = y - c * e['b']
-    rg = r * g
-    Acg = e['A'] * c * g
-    return dict(eta=e['eta'] + Acg * d, J=e['J'] + Acg * e['A'] * c, b=a * (e['b'] + e['C'] * c * g * d),
-                A=a * e['A'] * rg, C=a * a * e['C'] * rg + q)
-
-
-def _combine(i, j):
-    inv = 1.0 / (1.0 + i['C'] * j['J'])
-    return dict(A=j['A'] * inv * i['A'], b=j['A'] * inv * (i['b'] + i['C'] * j['eta']) + j['b'],
-                C=j['A'] * inv * j['A'] * i['C'] + j['C'], eta=i['A'] * inv * (j['eta'] - j['J'] * i['b']) + i['eta'],
-                J=i['A'] * inv * i['A'] * j['J'] + i['J'])
-
-
-def _apply(e, m, P):
-    inv = 1.0 / (1.0 + e['J'] * P)
-    return e['A'] * inv * (m + P * e['eta']) + e['b'], e['A'] * inv * e['A'] * P + e['C']
-
-
-def _back(e, eta, J):
-    inv = 1.0 / (1.0 + e['C'] * J)
-    return e['A'] * inv * (eta - J * e['b']) + e['eta'], e['A'] * inv * e['A'] * J + e['J']
-
-
-def _smooth_segment(y, r, a, c, q, m, P, eta, J):
-    """Filter frames y, r [L][n] from the predicted belief (m, P), fuse with the information (eta, J) about the state
-    behind them, RTS backwards.  Returns the smoothed means, variances [L][n] and the predicted belief behind."""
-    L = y.shape[0]
-    mf, Pf = np.empty_like(y), np.empty_like(y)
-    for t in range(L):
-        g = 1.0 / (P * c * c + r[t])
-        mf[t] = m + P * c * g * (y[t] - c * m)
-        Pf[t] = P * r[t] * g
-        m, P = a * mf[t], a * a * Pf[t] + q
-    m_out, P_out = m, P
-    inv = 1.0 / (1.0 + J * P)
-    ms_n, Ps_n = (m + P * eta) * inv, P * inv
-    ms, Ps = np.empty_like(y), np.empty_like(y)
-    for t in range(L - 1, -1, -1):
-        Pp = a * a * Pf[t] + q
-        Gn = a * Pf[t] / Pp
-        ms_n = mf[t] + Gn * (ms_n - a * mf[t])
-        Ps_n = Pf[t] * q / Pp + Gn * Gn * Ps_n
-        ms[t], Ps[t] = ms_n, Ps_n
-    return ms, Ps, m_out, P_out
+import window_ref as wr
+from window_ref import B, BAR, G, H, TOL, _apply, _back, _combine, _identity, _append, _smooth_segment
 
 
 def _chains(seed, n, T, a, c, offset):
@@ -97,7 +43,7 @@ def _chains(seed, n, T, a, c, offset):
     return y, r, s, m0, S0
 
 
-def _check(seed, a, c, offset, n=48, T=B * 41 + 5):
+def _check(seed, a, c, offset, n=48, T=B * 41 + 5, record=None):
     y, r, q, m0, S0 = _chains(seed, n, T, a, c, offset)
     nc = (T + B - 1) // B
     elems = []
@@ -129,6 +75,8 @@ def _check(seed, a, c, offset, n=48, T=B * 41 + 5):
             hb = _combine(hb, elems[j])
         ok_f = np.full(n, True) if cut_f else np.abs(hf['A']) <= TOL
         ok_b = np.full(n, True) if cut_b else np.abs(hb['A']) <= TOL
+        if record is not None:
+            record.append((cut_f, cut_b, np.abs(hf['A']), np.abs(hb['A']), ok_f & ok_b))
         for ok, cut in ((ok_f, cut_f), (ok_b, cut_b)):
             if not cut:
                 n_pass += int(ok.sum())
@@ -187,3 +135,76 @@ def test_windows_that_forget_reproduce_the_exact_entry_and_edge_beliefs():
     print(f'{n_pass} of {n_pass + n_fail} windows qualify ({100 * share:.1f} %)')
     assert n_pass > 0 and n_fail > 0
     assert 0.2 <= share <= 0.8, share
+
+
+def test_classify_agrees_with_the_restatement_of_the_check():
+    """window_ref.classify (what the GPU tests predict the kernel's fail marks with) against the halo compositions,
+    cut rules and verdicts that _check derives on its own."""
+    for seed, a, c, offset in CASES:
+        n, T = 48, B * 41 + 5
+        y, r, q, _, _ = _chains(seed, n, T, a, c, offset)
+        rec = []
+        _check(seed, a, c, offset, record=rec)
+        cls = wr.classify(y, r, a, c, q, T)
+        assert cls['fail'].shape == (len(rec), n)
+        for wg, (cut_f, cut_b, A_f, A_b, ok) in enumerate(rec):
+            assert (cls['cut_front'][wg], cls['cut_back'][wg]) == (cut_f, cut_b), wg
+            if not cut_f:
+                np.testing.assert_array_equal(cls['A_front'][wg], A_f)
+            if not cut_b:
+                np.testing.assert_array_equal(cls['A_back'][wg], A_b)
+            np.testing.assert_array_equal(cls['fail'][wg], ~ok)
+        assert cls['cut_front'].tolist() == [True] + [False] * (len(rec) - 1)
+        assert cls['cut_back'].tolist() == [False] * (len(rec) - 2) + [True, True]      # 42 chunks = 8 * 5 + 2
+
+
+def _gpu_inputs():
+    yield 'general', wr.general_problem()
+    for D in (1, 3, 8):
+        yield f'width D={D} unit', wr.width_problem(D, False)
+        yield f'width D={D} general', wr.width_problem(D, True)
+    for kind in ('low', 'high'):
+        yield f'clip {kind}', wr.clip_problem(kind)
+    for T in wr.FAIL_T:
+        yield f'fail pattern T={T}', wr.fail_pattern_problem(T)
+    for M, r0 in wr.OUTLIERS:
+        yield f'outlier {M:g}', wr.outlier_problem(M, r0)
+
+
+def test_the_windowed_restatement_stays_within_the_bound_on_the_inputs_of_the_gpu_tests():
+    """window_ref.windowed_smooth (the float64 statement of what replay_window_block computes) against the exact
+    smoother on the inputs tests/test_gpu_smooth_window.py feeds the kernel: on every lane the check lets through, the
+    means within 2^-29 (front spread + back spread) / min(1, |a|) - and within 1e-7 of the chain's magnitude, a
+    hundredth of the bar the kernel is held to - and the variances within 2^-29 relative.  Lanes whose halos are both
+    cut are exact (float64 rounding of the other order of composition: 1e-11 of the magnitude)."""
+    n_stored = n_failed = 0
+    for name, p in _gpu_inputs():
+        r = wr.restate(p)
+        T = p['y'].shape[0]
+        stored = ~wr.group_mask(r['fail'], T)
+        scale = np.abs(r['ms_x']).max(axis=0) + 1.0
+        err = np.abs(r['ms'] - r['ms_x'])
+        bound = wr.group_mask(r['bound'], T) + 1e-11 * scale
+        worst_b = float((err / bound)[stored].max())
+        worst_s = float((err / scale)[stored].max())
+        worst_P = float((np.abs(r['Ps'] - r['Ps_x']) / r['Ps_x'])[stored].max())
+        print(f'{name}: {int(r["fail"].sum())} of {r["fail"].size} lanes fail; stored lanes: means {worst_b:.3g} of the '
+              f'bound, {worst_s:.3g} of the magnitude, variances {worst_P:.3g} relative')
+        assert worst_b <= 1.0, (name, worst_b)
+        assert worst_s <= 1e-7, (name, worst_s)
+        assert worst_P <= BAR, (name, worst_P)
+        n_stored += int((~r['fail']).sum())
+        n_failed += int(r['fail'].sum())
+    assert n_stored > 0 and n_failed > 0
+
+
+def test_the_fail_pattern_inputs_have_no_borderline_halo():
+    """The GPU test of the fail pattern asks the kernel's float32 verdicts to EQUAL the float64 ones: every halo of
+    its inputs is far from the tolerance (|A| <= 2^-34 or >= 2^-26)."""
+    for T in wr.FAIL_T:
+        ch = wr.chains(wr.fail_pattern_problem(T))
+        cls = wr.classify(ch['y'], ch['var'], ch['a'], ch['c'], ch['q_s'], T)
+        for A, cut in ((cls['A_front'], cls['cut_front']), (cls['A_back'], cls['cut_back'])):
+            A = A[~cut]
+            assert ((A <= 2.0 ** -34) | (A >= 2.0 ** -26)).all(), (T, A[(A > 2.0 ** -34) & (A < 2.0 ** -26)])
+        print(T, 'failing lanes per group:', cls['fail'].sum(axis=1).tolist())
