@@ -60,13 +60,7 @@ __global__ __launch_bounds__(64) void dense_summarize_kernel(DenseGeom G, DenseM
 #pragma unroll
     for (int a = 0; a < D; ++a) xl[a] = m.a[a];
     belief_update_obs<D>(obs, k, 0, xl, m, P);
-    double* r = first + (size_t)k * (D + D * D);
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      r[a] = m.a[a];
-#pragma unroll
-      for (int b = 0; b < D; ++b) r[D + a * D + b] = P.a[a][b];
-    }
+    dense_store_rec<D>(first + (size_t)k * (D + D * D), 1, m, P);
   }
 }
 
@@ -138,15 +132,7 @@ __global__ __launch_bounds__(2 * kDenseCB) void dense_scan_blocks_kernel(DenseGe
   // every thread of a half carries its own copy of the running state (same arithmetic, same value)
   Vec<double, D> cv = vec_zero<double, D>();
   Mat<double, D> cM = mat_zero<double, D>();
-  if (!rev) {
-    const double* f0 = first + (size_t)k * REC;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      cv.a[a] = f0[a];
-#pragma unroll
-      for (int b = 0; b < D; ++b) cM.a[a][b] = f0[D + a * D + b];
-    }
-  }
+  if (!rev) dense_load_rec<D>(first + (size_t)k * REC, 1, cv, cM);
   const int rounds = (nblk + kDenseCB - 1) / kDenseCB;
   for (int r = 0; r < rounds; ++r) {
     const int q = (rev ? rounds - 1 - r : r) * kDenseCB + i;
@@ -173,17 +159,32 @@ __global__ __launch_bounds__(2 * kDenseCB) void dense_scan_blocks_kernel(DenseGe
       if (i + 1 < kDenseCB) delem_back(load_delem<double, D>(mine + (i + 1), kDenseCB), v, Mx);
       delem_back(load_delem<double, D>(mine, kDenseCB), cv, cM);
     }
-    if (live) {
-      double* w = (rev ? bsuffix : bprior) + ((size_t)q * G.K + k) * REC;
-#pragma unroll
-      for (int a = 0; a < D; ++a) {
-        w[a] = v.a[a];
-#pragma unroll
-        for (int b = 0; b < D; ++b) w[D + a * D + b] = Mx.a[a][b];
-      }
-    }
+    if (live) dense_store_rec<D>((rev ? bsuffix : bprior) + ((size_t)q * G.K + k) * REC, 1, v, Mx);
     __syncthreads();
   }
+}
+
+// What a replay lane starts from, for the lane of keypoint k whose frames are covered by the elements ea .. eb (the
+// extended filter's half-chunk elements; one element, ea == eb == the chunk, everywhere else): (m, P) the filtered
+// belief of the frame before element ea - the block's incoming belief through the exclusive prefix of ea inside its
+// block of 64, or the prior itself for chunk 0, which replays frame 0's update - and (eta, J) what all frames after
+// element eb say about its last frame - the block's outgoing information pulled back through the exclusive suffix of
+// eb.  suf == bsuffix == nullptr (a forward-only kernel): eta and J are left alone.
+template <int D>
+__device__ __forceinline__ void dense_chunk_boundary(const DenseGeom& G, const DenseModelPtrs& M, int k, int ea, int eb,
+                                                     const double* __restrict__ pre, const double* __restrict__ suf,
+                                                     const double* __restrict__ bprior,
+                                                     const double* __restrict__ bsuffix, Vec<double, D>& m,
+                                                     Mat<double, D>& P, Vec<double, D>& eta, Mat<double, D>& J) {
+  constexpr int REC = D + D * D;
+  constexpr int NV = delem_doubles<D>();
+  const int blk = ea / kDenseCB, ia = ea % kDenseCB, ib = eb % kDenseCB;
+  dense_load_rec<D>(bprior + ((size_t)blk * G.K + k) * REC, 1, m, P);
+  if (bsuffix) dense_load_rec<D>(bsuffix + ((size_t)blk * G.K + k) * REC, 1, eta, J);   // (both in flight together)
+  if (ia > 0) delem_apply(load_delem<double, D>(pre + ((size_t)(ea - 1) * G.K + k) * NV), m, P);
+  if (bsuffix && ib + 1 < kDenseCB && eb + 1 < G.ncs)
+    delem_back(load_delem<double, D>(suf + ((size_t)(eb + 1) * G.K + k) * NV), eta, J);
+  if (ea == 0) load_prior<D>(M, k, m, P);
 }
 
 template <int D, bool EKF, typename Obs, bool SCORE = false>
@@ -206,30 +207,12 @@ __global__ __launch_bounds__(64) void dense_replay_kernel(DenseGeom G, DenseMode
   Mat<double, D> F, sQ;
   bool fid;
   load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
-  constexpr int NV = delem_doubles<D>();
   Vec<double, D> m, eta;
   Mat<double, D> P, J;
   // this lane's frames are covered by the elements ea .. eb (one element on the linear path)
   const int sub = G.B / G.Bs;
-  const int ea = j * sub, eb = min(ea + sub - 1, G.ncs - 1);
-  const int blk = ea / kDenseCB, ia = ea % kDenseCB, ib = eb % kDenseCB;
-  const double* rp = bprior + ((size_t)blk * G.K + k) * REC;
-  const double* rs = bsuffix + ((size_t)blk * G.K + k) * REC;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    m.a[a] = rp[a];
-    eta.a[a] = rs[a];
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      P.a[a][b] = rp[D + a * D + b];
-      J.a[a][b] = rs[D + a * D + b];
-    }
-  }
-  // exclusive prefix of the first / exclusive suffix of the last element inside the block of 64
-  if (ia > 0) delem_apply(load_delem<double, D>(pre + ((size_t)(ea - 1) * G.K + k) * NV), m, P);
-  if (ib + 1 < kDenseCB && eb + 1 < G.ncs)
-    delem_back(load_delem<double, D>(suf + ((size_t)(eb + 1) * G.K + k) * NV), eta, J);
-  if (j == 0) load_prior<D>(M, k, m, P);   // chunk 0 replays frame 0's update of the prior itself
+  const int ea = j * sub;
+  dense_chunk_boundary<D>(G, M, k, ea, min(ea + sub - 1, G.ncs - 1), pre, suf, bprior, bsuffix, m, P, eta, J);
   const int t0 = j * G.B, len = min(G.B, G.T - t0);
   double ll = 0.0, ch = 0.0;
   dense_replay_chunk_obs<D, EKF, Obs, SCORE>(obs, G.K, k, t0, len, F, sQ, fid, m, P, eta, J,
@@ -329,6 +312,37 @@ static GenericLayout generic_layout(int T, int K, int D, int nc, char* base) {
   return L;
 }
 
+// One element per replay chunk (every driver but the pinhole filter's half-chunk elements).
+static DenseGeom dense_geom(int T, int K, int O, int B) {
+  const int nc = (T + B - 1) / B;
+  return DenseGeom{K, T, O, B, nc, B, nc};
+}
+
+// D2: both scan levels over the elements in L.elems.
+template <int D>
+static void dense_scan_launch(const DenseGeom& G, const GenericLayout& L, const Gate& gate, hipStream_t st) {
+  const int nblk = (G.ncs + kDenseCB - 1) / kDenseCB;
+  hipLaunchKernelGGL(dense_scan_kernel<D>, dim3(G.K, nblk), dim3(2 * kDenseCB), 0, st, G, L.elems, L.pre, L.suf, L.agg,
+                     gate);
+  hipLaunchKernelGGL(dense_scan_blocks_kernel<D>, dim3(G.K), dim3(2 * kDenseCB), 0, st, G, nblk, L.first, L.agg,
+                     L.bprior, L.bsuffix, gate);
+}
+
+// D1 + D2, what every driver of the generic organisation runs before its own replay kernel: chunk elements of `obs`,
+// then the scan, each under its profile scope (string literals: ProfScope keeps the pointer).
+template <int D, typename Obs>
+static void dense_prelude(const DenseGeom& G, const DenseModelPtrs& M, const double* s, const Obs& obs,
+                          const GenericLayout& L, const Gate& gate, const char* summarize_scope,
+                          const char* scan_scope, hipStream_t st) {
+  {
+    ProfScope ps(summarize_scope, st);
+    hipLaunchKernelGGL((dense_summarize_kernel<D, Obs>), dim3((G.K * G.ncs + 63) / 64), dim3(64), 0, st, G, M, s, obs,
+                       L.elems, L.first, gate);
+  }
+  ProfScope ps(scan_scope, st);
+  dense_scan_launch<D>(G, L, gate, st);
+}
+
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O) {
   const int B = dense_chunk(T, K), nc = (T + B - 1) / B;
   switch (dense_path(T, K, D, O)) {
@@ -347,11 +361,7 @@ int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const De
   // shuffles and the filtered beliefs in LDS (eks_dense_wave.hip); wide ones stream keypoint-major
   const DensePath path = dense_path(T, K, D, O);
   if (path == kDenseWave) return dense_wave_smooth(d, y, var, Mm, ms, Vs, ws, ws_bytes, st);
-  DenseGeom G{K, T, O, dense_chunk(T, K), 0, 0, 0};
-  G.nc = (T + G.B - 1) / G.B;
-  G.Bs = G.B;
-  G.ncs = G.nc;
-  const int nblk = (G.nc + kDenseCB - 1) / kDenseCB;
+  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
   const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
   if (path == kDenseRuns) {
     const RunsLayout L = runs_layout(K, D, G.nc, static_cast<char*>(ws));
@@ -372,44 +382,33 @@ int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const De
                              nullptr, nullptr, L.chunk_in, L.chunk_out, ms, Vs, vs_diag, st);
   }
   const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
-  double *elems = L.elems, *pre = L.pre, *suf = L.suf, *agg = L.agg, *bprior = L.bprior, *bsuffix = L.bsuffix,
-         *filt = L.filt, *first = L.first;
   const int lanes = K * G.nc;
   const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
   const Gate open{nullptr, 0.0};
-  // (EKS_DENSE_TREE_SCAN: the keypoint-major summarize / replay around the tree scan of whole elements)
-  const bool wide = dense_wide_covers(D, O, G.B);
   EKS_DISPATCH_D(D, {
     const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
-    {
-      ProfScope ps("dense_summarize", st);
-      if (wide) {
-        const int rc = dense_wide_summarize(T, K, D, O, G.B, G.nc, M, Mm.s, y, var, nullptr, elems, 0, first, st);
+    if (dense_wide_covers(D, O, G.B)) {
+      // (EKS_DENSE_TREE_SCAN: the keypoint-major summarize / replay around the tree scan of whole elements)
+      int rc;
+      {
+        ProfScope ps("dense_summarize", st);
+        rc = dense_wide_summarize(T, K, D, O, G.B, G.nc, M, Mm.s, y, var, nullptr, L.elems, 0, L.first, st);
         if (rc != EKS_OK) return rc;
-      } else {
-        hipLaunchKernelGGL((dense_summarize_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64),
-                           dim3(64), 0, st, G, M, Mm.s, obs, elems, first, open);
       }
-    }
-    {
-      ProfScope ps("dense_scan", st);
-      const dim3 sgrid(K, nblk);
-      hipLaunchKernelGGL(dense_scan_kernel<DD>, sgrid, dim3(2 * kDenseCB), 0, st, G, elems, pre, suf,
-                         agg, open);
-      hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk,
-                         first, agg, bprior, bsuffix, open);
-    }
-    {
+      {
+        ProfScope ps("dense_scan", st);
+        dense_scan_launch<DD>(G, L, open, st);
+      }
       ProfScope ps("dense_replay", st);
-      if (wide) {
-        const int rc = dense_wide_replay(T, K, D, O, G.B, G.nc, M, Mm.s, y, var, nullptr, nullptr, nullptr, pre, suf,
-                                         bprior, bsuffix, nullptr, nullptr, ms, Vs, vs_diag, st);
-        if (rc != EKS_OK) return rc;
-      } else {
-        hipLaunchKernelGGL((dense_replay_kernel<DD, false, LinearObs<DD>>), dim3((lanes + 63) / 64),
-                           dim3(64), 0, st, G, M, Mm.s, obs, pre, suf, bprior, bsuffix, filt, ms, Vs,
-                           vs_diag, nullptr, nullptr, nullptr, open);
-      }
+      rc = dense_wide_replay(T, K, D, O, G.B, G.nc, M, Mm.s, y, var, nullptr, nullptr, nullptr, L.pre, L.suf, L.bprior,
+                             L.bsuffix, nullptr, nullptr, ms, Vs, vs_diag, st);
+      if (rc != EKS_OK) return rc;
+    } else {
+      dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_summarize", "dense_scan", st);
+      ProfScope ps("dense_replay", st);
+      hipLaunchKernelGGL((dense_replay_kernel<DD, false, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
+                         Mm.s, obs, L.pre, L.suf, L.bprior, L.bsuffix, L.filt, ms, Vs, vs_diag, nullptr, nullptr,
+                         nullptr, open);
     }
   })
   return hip_status(hipGetLastError());
@@ -430,31 +429,13 @@ __global__ __launch_bounds__(64) void dense_increments_kernel(DenseGeom G, Dense
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= G.K * G.nc) return;
   constexpr int REC = D + D * D;
-  constexpr int NV = delem_doubles<D>();
   const int k = idx % G.K, j = idx / G.K;
   Mat<double, D> F, sQ;
   bool fid;
   load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
   Vec<double, D> m, eta;
   Mat<double, D> P, J;
-  // one element per lane (Bs == B): boundaries as in dense_replay_kernel
-  const int blk = j / kDenseCB, ia = j % kDenseCB;
-  const double* rp = bprior + ((size_t)blk * G.K + k) * REC;
-  const double* rs = bsuffix + ((size_t)blk * G.K + k) * REC;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    m.a[a] = rp[a];
-    eta.a[a] = rs[a];
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      P.a[a][b] = rp[D + a * D + b];
-      J.a[a][b] = rs[D + a * D + b];
-    }
-  }
-  if (ia > 0) delem_apply(load_delem<double, D>(pre + ((size_t)(j - 1) * G.K + k) * NV), m, P);
-  if (ia + 1 < kDenseCB && j + 1 < G.nc)
-    delem_back(load_delem<double, D>(suf + ((size_t)(j + 1) * G.K + k) * NV), eta, J);
-  if (j == 0) load_prior<D>(M, k, m, P);   // chunk 0 replays frame 0's update of the prior itself
+  dense_chunk_boundary<D>(G, M, k, j, j, pre, suf, bprior, bsuffix, m, P, eta, J);   // one element per lane (Bs == B)
   const int t0 = j * G.B, len = min(G.B, G.T - t0);
   dense_increments_chunk<D, Obs>(obs, G.K, k, t0, len, F, sQ, fid, m, P, eta, J, filt + (size_t)t0 * REC * G.K + k, out,
                                  (size_t)G.K);
@@ -471,31 +452,17 @@ int dense_increments(const eks_dims_t& d, const float* y, const float* var, cons
                      float* lag1, float* dmean, float* dV, void* ws, size_t ws_bytes, hipStream_t st) {
   const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
   if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
-  DenseGeom G{K, T, O, dense_chunk(T, K), 0, 0, 0};
-  G.nc = (T + G.B - 1) / G.B;
-  G.Bs = G.B;
-  G.ncs = G.nc;
+  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
   if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
   if (ws_bytes < dense_increments_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
-  const int nblk = (G.nc + kDenseCB - 1) / kDenseCB, lanes = K * G.nc;
+  const int lanes = K * G.nc;
   const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
   const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
   const DenseIncrementsOut out{ms, Vs, lag1, dmean, dV, (d.flags & EKS_FLAG_VS_DIAG) != 0, T};
   const Gate open{nullptr, 0.0};
   EKS_DISPATCH_D(D, {
     const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
-    {
-      ProfScope ps("dense_increments_summarize", st);
-      hipLaunchKernelGGL((dense_summarize_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
-                         Mm.s, obs, L.elems, L.first, open);
-    }
-    {
-      ProfScope ps("dense_increments_scan", st);
-      hipLaunchKernelGGL(dense_scan_kernel<DD>, dim3(K, nblk), dim3(2 * kDenseCB), 0, st, G, L.elems, L.pre, L.suf,
-                         L.agg, open);
-      hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk, L.first, L.agg,
-                         L.bprior, L.bsuffix, open);
-    }
+    dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_increments_summarize", "dense_increments_scan", st);
     {
       ProfScope ps("dense_increments_replay", st);
       hipLaunchKernelGGL((dense_increments_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
@@ -519,31 +486,13 @@ __global__ __launch_bounds__(64) void dense_em_kernel(DenseGeom G, DenseModelPtr
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= G.K * G.nc) return;
   constexpr int REC = D + D * D;
-  constexpr int NV = delem_doubles<D>();
   const int k = idx % G.K, j = idx / G.K;
   Mat<double, D> F, sQ;
   bool fid;
   load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
   Vec<double, D> m, eta;
   Mat<double, D> P, J;
-  // one element per lane (Bs == B): boundaries as in dense_replay_kernel
-  const int blk = j / kDenseCB, ia = j % kDenseCB;
-  const double* rp = bprior + ((size_t)blk * G.K + k) * REC;
-  const double* rs = bsuffix + ((size_t)blk * G.K + k) * REC;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    m.a[a] = rp[a];
-    eta.a[a] = rs[a];
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      P.a[a][b] = rp[D + a * D + b];
-      J.a[a][b] = rs[D + a * D + b];
-    }
-  }
-  if (ia > 0) delem_apply(load_delem<double, D>(pre + ((size_t)(j - 1) * G.K + k) * NV), m, P);
-  if (ia + 1 < kDenseCB && j + 1 < G.nc)
-    delem_back(load_delem<double, D>(suf + ((size_t)(j + 1) * G.K + k) * NV), eta, J);
-  if (j == 0) load_prior<D>(M, k, m, P);   // chunk 0 replays frame 0's update of the prior itself
+  dense_chunk_boundary<D>(G, M, k, j, j, pre, suf, bprior, bsuffix, m, P, eta, J);   // one element per lane (Bs == B)
   const int t0 = j * G.B, len = min(G.B, G.T - t0);
   const int w = diag ? D : D * D;
   dense_em_chunk<D, Obs>(obs, k, t0, len, F, sQ, fid, m, P, eta, J, filt + (size_t)t0 * REC * G.K + k, (size_t)G.K,
@@ -563,13 +512,10 @@ int dense_em_stats(const eks_dims_t& d, const float* y, const float* var, const 
                    size_t ws_bytes, hipStream_t st) {
   const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
   if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
-  DenseGeom G{K, T, O, dense_chunk(T, K), 0, 0, 0};
-  G.nc = (T + G.B - 1) / G.B;
-  G.Bs = G.B;
-  G.ncs = G.nc;
+  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
   if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
   if (ws_bytes < dense_em_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
-  const int nblk = (G.nc + kDenseCB - 1) / kDenseCB, lanes = K * G.nc;
+  const int lanes = K * G.nc;
   const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
   const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
   double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + L.bytes);
@@ -577,18 +523,7 @@ int dense_em_stats(const eks_dims_t& d, const float* y, const float* var, const 
   const Gate open{nullptr, 0.0};
   EKS_DISPATCH_D(D, {
     const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
-    {
-      ProfScope ps("dense_em_summarize", st);
-      hipLaunchKernelGGL((dense_summarize_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
-                         Mm.s, obs, L.elems, L.first, open);
-    }
-    {
-      ProfScope ps("dense_em_scan", st);
-      hipLaunchKernelGGL(dense_scan_kernel<DD>, dim3(K, nblk), dim3(2 * kDenseCB), 0, st, G, L.elems, L.pre, L.suf,
-                         L.agg, open);
-      hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk, L.first, L.agg,
-                         L.bprior, L.bsuffix, open);
-    }
+    dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_em_summarize", "dense_em_scan", st);
     {
       ProfScope ps("dense_em_replay", st);
       hipLaunchKernelGGL((dense_em_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s,
@@ -613,25 +548,13 @@ __global__ __launch_bounds__(64) void dense_innov_kernel(DenseGeom G, DenseModel
                                                         double* __restrict__ part) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= G.K * G.nc) return;
-  constexpr int REC = D + D * D;
-  constexpr int NV = delem_doubles<D>();
   const int k = idx % G.K, j = idx / G.K;
   Mat<double, D> F, sQ;
   bool fid;
   load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
-  Vec<double, D> m;
-  Mat<double, D> P;
-  // one element per lane (Bs == B): the forward boundary as in dense_replay_kernel
-  const int blk = j / kDenseCB, ia = j % kDenseCB;
-  const double* rp = bprior + ((size_t)blk * G.K + k) * REC;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    m.a[a] = rp[a];
-#pragma unroll
-    for (int b = 0; b < D; ++b) P.a[a][b] = rp[D + a * D + b];
-  }
-  if (ia > 0) delem_apply(load_delem<double, D>(pre + ((size_t)(j - 1) * G.K + k) * NV), m, P);
-  if (j == 0) load_prior<D>(M, k, m, P);   // chunk 0 replays frame 0's update of the prior itself
+  Vec<double, D> m, eta;
+  Mat<double, D> P, J;
+  dense_chunk_boundary<D>(G, M, k, j, j, pre, nullptr, bprior, nullptr, m, P, eta, J);   // forward boundary only
   const int t0 = j * G.B, len = min(G.B, G.T - t0);
   const double ll = dense_innov_chunk<D, Obs>(obs, G.K, G.O, k, t0, len, F, sQ, fid, m, P, out);
   if (part) part[idx] = ll;
@@ -649,13 +572,10 @@ int dense_innovations(const eks_dims_t& d, const float* y, const float* var, con
                       hipStream_t st) {
   const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
   if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
-  DenseGeom G{K, T, O, dense_chunk(T, K), 0, 0, 0};
-  G.nc = (T + G.B - 1) / G.B;
-  G.Bs = G.B;
-  G.ncs = G.nc;
+  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
   if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
   if (ws_bytes < dense_innovations_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
-  const int nblk = (G.nc + kDenseCB - 1) / kDenseCB, lanes = K * G.nc;
+  const int lanes = K * G.nc;
   const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
   const GenericLayout L = generic_layout(0, K, D, G.nc, static_cast<char*>(ws));
   double* part = loglik ? reinterpret_cast<double*>(static_cast<char*>(ws) + L.bytes) : nullptr;
@@ -663,18 +583,7 @@ int dense_innovations(const eks_dims_t& d, const float* y, const float* var, con
   const Gate open{nullptr, 0.0};
   EKS_DISPATCH_D(D, {
     const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
-    {
-      ProfScope ps("dense_innov_summarize", st);
-      hipLaunchKernelGGL((dense_summarize_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
-                         Mm.s, obs, L.elems, L.first, open);
-    }
-    {
-      ProfScope ps("dense_innov_scan", st);
-      hipLaunchKernelGGL(dense_scan_kernel<DD>, dim3(K, nblk), dim3(2 * kDenseCB), 0, st, G, L.elems, L.pre, L.suf,
-                         L.agg, open);
-      hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk, L.first, L.agg,
-                         L.bprior, L.bsuffix, open);
-    }
+    dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_innov_summarize", "dense_innov_scan", st);
     {
       ProfScope ps("dense_innov_replay", st);
       hipLaunchKernelGGL((dense_innov_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s,
@@ -711,33 +620,19 @@ int dense_score(const eks_dims_t& d, const float* y, const double* rconst, const
     // any D <= 6, O <= 64: the generic kernels with constant variances (layout of dense_smooth: prefix / suffix
     // elements per chunk, the filtered-belief stream; per-chunk partial sums where the chunk elements were - they
     // are dead once the scan has run)
-    DenseGeom G{K, T, O, B, nc, B, nc};
-    const int nblk = (nc + kDenseCB - 1) / kDenseCB;
+    const DenseGeom G = dense_geom(T, K, O, B);
     const GenericLayout L = generic_layout(T, K, D, nc, static_cast<char*>(ws));
-    double *elems = L.elems, *pre = L.pre, *suf = L.suf, *agg = L.agg, *bprior = L.bprior, *bsuffix = L.bsuffix,
-           *filt = L.filt, *first = L.first;
-    double* part_ll = elems;
-    double* part_score = elems + (size_t)nc * K;
+    double* part_ll = L.elems;
+    double* part_score = L.elems + (size_t)nc * K;
     const int lanes = K * nc;
     const Gate open{nullptr, 0.0};
     EKS_DISPATCH_D(D, {
       const ConstLinearObs<DD> obs = make_const_linear_obs<DD>(y, rconst, K, O, M);
-      {
-        ProfScope ps("dense_score_summarize", st);
-        hipLaunchKernelGGL((dense_summarize_kernel<DD, ConstLinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st,
-                           G, M, Mm.s, obs, elems, first, open);
-      }
-      {
-        ProfScope ps("dense_score_scan", st);
-        hipLaunchKernelGGL(dense_scan_kernel<DD>, dim3(K, nblk), dim3(2 * kDenseCB), 0, st, G, elems, pre, suf, agg,
-                           open);
-        hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk, first, agg,
-                           bprior, bsuffix, open);
-      }
+      dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_score_summarize", "dense_score_scan", st);
       ProfScope ps("dense_score_replay", st);
       hipLaunchKernelGGL((dense_replay_kernel<DD, false, ConstLinearObs<DD>, true>), dim3((lanes + 63) / 64), dim3(64),
-                         0, st, G, M, Mm.s, obs, pre, suf, bprior, bsuffix, filt, nullptr, nullptr, 0, nullptr,
-                         part_ll, part_score, open);
+                         0, st, G, M, Mm.s, obs, L.pre, L.suf, L.bprior, L.bsuffix, L.filt, nullptr, nullptr, 0,
+                         nullptr, part_ll, part_score, open);
     })
     const int rc0 = hip_status(hipGetLastError());
     if (rc0 != EKS_OK) return rc0;
@@ -905,25 +800,25 @@ int ekf_smooth(const eks_dims_t& d, int n_data_keypoints, const float* y, const 
 // of sweeps does not depend on the frames per lane and the chunk length is chosen for the cost of a sweep.
 static int affine_chunk(int T, int K) { return dense_chunk(T, K); }
 
-static size_t affine_ws_layout(int T, int K, int D, bool smooth, double** ptrs, char* base) {
+// The generic layout (its filtered-belief stream only with the smoother) and two tail regions: the chunks'
+// log-likelihoods and the sweep's largest change of a linearisation point.
+struct AffineLayout {
+  GenericLayout g;
+  double *ll_chunk, *resid;
+  size_t bytes;
+};
+static AffineLayout affine_layout(int T, int K, int D, bool smooth, char* base) {
   const int B = affine_chunk(T, K), nc = (T + B - 1) / B;
-  const int nblk = (nc + kDenseCB - 1) / kDenseCB;
-  const size_t nv = 3 * D * D + 2 * D + 1, rec = D + D * D;
-  const size_t sizes[10] = {(size_t)nc * K * nv * 8,   (size_t)nc * K * nv * 8,
-                            (size_t)nc * K * nv * 8,   (size_t)nblk * K * nv * 8,
-                            (size_t)nblk * K * rec * 8, (size_t)nblk * K * rec * 8,
-                            smooth ? (size_t)T * K * rec * 8 : 0, (size_t)K * rec * 8,
-                            (size_t)nc * K * 8,         8};
-  size_t off = 0;
-  for (int i = 0; i < 10; ++i) {
-    if (ptrs) ptrs[i] = reinterpret_cast<double*>(base + off);
-    off += align_up(sizes[i], 256);
-  }
-  return off;
+  AffineLayout L;
+  L.g = generic_layout(smooth ? T : 0, K, D, nc, base);
+  L.ll_chunk = reinterpret_cast<double*>(base + L.g.bytes);
+  L.resid = reinterpret_cast<double*>(base + L.g.bytes + align_up((size_t)nc * K * 8, 256));
+  L.bytes = L.g.bytes + align_up((size_t)nc * K * 8, 256) + align_up(8, 256);
+  return L;
 }
 
 size_t ekf_affine_workspace_bytes(int T, int K, int D, int smooth) {
-  return affine_ws_layout(T, K, D, smooth != 0, nullptr, nullptr);
+  return affine_layout(T, K, D, smooth != 0, nullptr).bytes;
 }
 
 __global__ __launch_bounds__(64) void affine_finish_kernel(int K, int nc, const double* __restrict__ ll_chunk,
@@ -950,15 +845,11 @@ int ekf_affine_sweep(const eks_dims_t& d, int n_data_keypoints, const float* y, 
   if ((var == nullptr) == (rconst == nullptr)) return EKS_ERR_SHAPE;
   const bool smooth = ms != nullptr;
   if (ws_bytes < ekf_affine_workspace_bytes(T, K, D, smooth)) return EKS_ERR_WORKSPACE;
-  double* w[10];
-  affine_ws_layout(T, K, D, smooth, w, static_cast<char*>(ws));
-  double *elems = w[0], *pre = w[1], *suf = w[2], *agg = w[3], *bprior = w[4], *bsuffix = w[5],
-         *filt = w[6], *first = w[7], *ll_chunk = w[8], *resid = w[9];
-  DenseGeom G{K, T, O, affine_chunk(T, K), 0, 0, 0};
-  G.nc = (T + G.B - 1) / G.B;
-  G.Bs = G.B;
-  G.ncs = G.nc;
-  const int nblk = (G.nc + kDenseCB - 1) / kDenseCB, lanes = K * G.nc;
+  const AffineLayout A = affine_layout(T, K, D, smooth, static_cast<char*>(ws));
+  const GenericLayout& L = A.g;
+  double *ll_chunk = A.ll_chunk, *resid = A.resid;
+  const DenseGeom G = dense_geom(T, K, O, affine_chunk(T, K));
+  const int lanes = K * G.nc;
   const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, nullptr, Mm.Q};
   const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
   const Gate open{nullptr, 0.0};
@@ -966,23 +857,12 @@ int ekf_affine_sweep(const eks_dims_t& d, int n_data_keypoints, const float* y, 
   if (e != hipSuccess) return hip_status(e);
   EKS_DISPATCH_D(D, {
     const AffineObs<DD> obs = make_affine_obs<DD>(y, var, rconst, K, Kd, O, jac, off);
-    {
-      ProfScope ps("ekf_affine_summarize", st);
-      hipLaunchKernelGGL((dense_summarize_kernel<DD, AffineObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
-                         Mm.s, obs, elems, first, open);
-    }
-    {
-      ProfScope ps("ekf_affine_scan", st);
-      hipLaunchKernelGGL(dense_scan_kernel<DD>, dim3(K, nblk), dim3(2 * kDenseCB), 0, st, G, elems, pre, suf, agg,
-                         open);
-      hipLaunchKernelGGL(dense_scan_blocks_kernel<DD>, dim3(K), dim3(2 * kDenseCB), 0, st, G, nblk, first, agg,
-                         bprior, bsuffix, open);
-    }
+    dense_prelude<DD>(G, M, Mm.s, obs, L, open, "ekf_affine_summarize", "ekf_affine_scan", st);
     {
       ProfScope ps("ekf_affine_replay", st);
       hipLaunchKernelGGL((dense_replay_kernel<DD, true, AffineObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G,
-                         M, Mm.s, obs, pre, suf, bprior, bsuffix, smooth ? filt : nullptr, ms, Vs, vs_diag, xlin,
-                         ll_chunk, resid, open);
+                         M, Mm.s, obs, L.pre, L.suf, L.bprior, L.bsuffix, smooth ? L.filt : nullptr, ms, Vs, vs_diag,
+                         xlin, ll_chunk, resid, open);
     }
   })
   hipLaunchKernelGGL(affine_finish_kernel, dim3(K), dim3(64), 0, st, K, G.nc, ll_chunk, resid, nll, change);

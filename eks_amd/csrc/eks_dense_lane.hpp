@@ -254,17 +254,17 @@ EKS_HD AffineObs<D> make_affine_obs(const float* y, const float* var, const doub
 }
 
 // Measurement update of the belief N(m, P) with frame t of keypoint k, one scalar observation at
-// a time (R_t diagonal).  Returns the frame's log-likelihood when LL is set.
-template <int D, bool LL = false, typename Obs>
-EKS_HD double belief_update_obs(const Obs& obs, int k, int t, const double* xl, Vec<double, D>& m,
-                                Mat<double, D>& P) {
-  double ll = 0.0;
+// a time (R_t diagonal).  acc(sigma, d, gd) sees each observation's innovation variance, innovation and
+// gain-weighted innovation before its update is applied.
+template <int D, typename Obs, typename Acc>
+EKS_HD void belief_update_obs_acc(const Obs& obs, int k, int t, const double* xl, Vec<double, D>& m,
+                                  Mat<double, D>& P, Acc&& acc) {
   obs.visit(t, k, xl, [&](const Vec<double, D>& h, double yv, double r) {
     const Vec<double, D> u = mat_vec(P, h);
     const double sigma = r + dot(h, u);
     const double g = rcp(sigma);
     const double d = yv - dot(h, m), gd = g * d;
-    if (LL) ll -= 0.5 * (kLog2Pi + log(sigma) + d * gd);
+    acc(sigma, d, gd);
 #pragma unroll
     for (int a = 0; a < D; ++a) {
       m.a[a] += u.a[a] * gd;
@@ -276,6 +276,16 @@ EKS_HD double belief_update_obs(const Obs& obs, int k, int t, const double* xl, 
         P.a[b][a] = pv;
       }
     }
+  });
+}
+
+// Returns the frame's log-likelihood when LL is set.
+template <int D, bool LL = false, typename Obs>
+EKS_HD double belief_update_obs(const Obs& obs, int k, int t, const double* xl, Vec<double, D>& m,
+                                Mat<double, D>& P) {
+  double ll = 0.0;
+  belief_update_obs_acc<D>(obs, k, t, xl, m, P, [&](double sigma, double d, double gd) {
+    if (LL) ll -= 0.5 * (kLog2Pi + log(sigma) + d * gd);
   });
   return ll;
 }
@@ -316,10 +326,153 @@ EKS_HD DElem<double, D> dense_smooth_element(const float* __restrict__ y, const 
   return dense_smooth_element_obs<D>(LinearObs<D>{y, var, K, O, M}, k, t0, len, F, sQ, f_identity);
 }
 
+// ---- one lane's chunk: the exact filter forwards into scratch records, the RTS recursion backwards ----------------
+// `filt` is a lane's scratch: len records of D + D*D doubles (filtered mean and covariance), written forwards and
+// read backwards.  fs: distance in doubles between consecutive fields of the records (1: a lane's records are
+// contiguous; K: the records of the K keypoints are interleaved field by field, so the lanes of a wave -
+// consecutive keypoints - read and write whole segments.  Per-lane contiguous records cost the wide
+// multicam shape 1.28 ms in the replay: every 8-byte access of a wave touched 64 different lines.)
+template <int D>
+EKS_HD void dense_store_rec(double* __restrict__ rec, size_t fs, const Vec<double, D>& m, const Mat<double, D>& P) {
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    rec[a * fs] = m.a[a];
+#pragma unroll
+    for (int b = 0; b < D; ++b) rec[(D + a * D + b) * fs] = P.a[a][b];
+  }
+}
+template <int D>
+EKS_HD void dense_load_rec(const double* __restrict__ rec, size_t fs, Vec<double, D>& m, Mat<double, D>& P) {
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    m.a[a] = rec[a * fs];
+#pragma unroll
+    for (int b = 0; b < D; ++b) P.a[a][b] = rec[(D + a * D + b) * fs];
+  }
+}
+
+// float32 outputs [T][K][D] and [T][K][D][D] (or its diagonal [T][K][D]); ko = t * K + k.  A null dst writes nothing.
+template <int D>
+EKS_HD void dense_store_vec(float* dst, size_t ko, const Vec<double, D>& v) {
+  if (!dst) return;
+#pragma unroll
+  for (int a = 0; a < D; ++a) EKS_STREAM_STORE(dst + ko * D + a, (float)v.a[a]);
+}
+template <int D>
+EKS_HD void dense_store_mat(float* dst, size_t ko, const Mat<double, D>& P, bool diag) {
+  if (!dst) return;
+  if (diag) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) EKS_STREAM_STORE(dst + ko * D + a, (float)P.a[a][a]);
+  } else {
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+      for (int b = 0; b < D; ++b) EKS_STREAM_STORE(dst + (ko * D + a) * D + b, (float)P.a[a][b]);
+  }
+}
+
+// The belief one frame on: (m, P) <- (F m, F P F^T + sQ).
+template <int D>
+EKS_HD void dense_predict(const Mat<double, D>& F, const Mat<double, D>& sQ, bool f_identity, Vec<double, D>& m,
+                          Mat<double, D>& P) {
+  if (!f_identity) {
+    m = mat_vec(F, m);
+    P = mat_mul_nt(mat_mul(F, P), F);
+  }
+  P = mat_add(P, sQ);
+}
+
+// Forwards over frames [t0, t0+len): predict (not into frame 0 of the sequence), update, write the record.  (m, P)
+// enters as the filtered belief of frame t0-1 (the prior itself when t0 == 0) and leaves as that of the chunk's last
+// frame.  hook(i, m) is called with the predicted mean of frame t0+i and returns the point to linearise the frame at
+// (null: the observation source's own).  filt == nullptr: no records.  Returns the chunk's log-likelihood with LL.
+struct DenseNoHook {
+  template <typename V>
+  EKS_HD const double* operator()(int, const V&) const { return nullptr; }
+};
+template <int D, bool LL, typename Obs, typename Hook = DenseNoHook>
+EKS_HD double dense_forward_chunk(const Obs& obs, int k, int t0, int len, const Mat<double, D>& F,
+                                  const Mat<double, D>& sQ, bool f_identity, Vec<double, D>& m, Mat<double, D>& P,
+                                  double* __restrict__ filt, size_t fs, Hook&& hook = Hook()) {
+  constexpr int REC = D + D * D;
+  double ll = 0.0;
+  for (int i = 0; i < len; ++i) {
+    const int t = t0 + i;
+    if (t > 0) dense_predict(F, sQ, f_identity, m, P);
+    ll += belief_update_obs<D, LL>(obs, k, t, hook(i, m), m, P);
+    if (filt) dense_store_rec<D>(filt + (size_t)i * REC * fs, fs, m, P);
+  }
+  return ll;
+}
+
+// What the backward walker knows about the transition from frame i to frame i+1 of the chunk (i = -1: from the
+// frame before the chunk): (mf, Pf) the filtered belief of frame i, FP = F Pf, Pp = F Pf F^T + sQ and its Cholesky
+// factor Lp, Z = Pp^-1 F Pf (the smoother gain is G = Z^T), dm = m' - F mf, (m_next, P_next) = (m', P') the smoothed
+// belief of frame i+1 and (m_s, P_s) that of frame i.
+template <int D>
+struct DenseTransition {
+  using V = const Vec<double, D>&;
+  using M = const Mat<double, D>&;
+  V mf;
+  M Pf, FP, Pp;
+  const CholF<double, D>& Lp;
+  M Z;
+  V dm, m_next;
+  M P_next;
+  V m_s;
+  M P_s;
+};
+
+// Backwards from the chunk's last frame: (m, P) its filtered belief, (eta_s, J_s) what all later frames say about
+// its state.  last(m_s, P_s) receives the smoothed last frame, step(i, tr) every transition from i = len-2 down to
+// i_end: 0, or -1 to include the transition out of the belief (m_in, P_in) that entered the chunk (there is none
+// when t0 == 0).  Only Pp is factored, never Q: singular Q or S0 are fine while Pp is positive definite.
+template <int D, typename Last, typename Step>
+EKS_HD void dense_backward_chunk(int t0, int len, int i_end, const Mat<double, D>& F, const Mat<double, D>& sQ,
+                                 bool f_identity, const Vec<double, D>& m_in, const Mat<double, D>& P_in,
+                                 const Vec<double, D>& m, const Mat<double, D>& P, const Vec<double, D>& eta_s,
+                                 const Mat<double, D>& J_s, const double* __restrict__ filt, size_t fs, Last&& last,
+                                 Step&& step) {
+  constexpr int REC = D + D * D;
+  Vec<double, D> m_s;
+  Mat<double, D> P_s;
+  double logdet;
+  condition_on_info(m, P, eta_s, J_s, m_s, P_s, logdet);      // smoothed last frame of the chunk
+  last(m_s, P_s);
+  for (int i = len - 2; i >= i_end; --i) {
+    Vec<double, D> mf;
+    Mat<double, D> Pf;
+    if (i >= 0) {
+      dense_load_rec<D>(filt + (size_t)i * REC * fs, fs, mf, Pf);
+    } else {                                                  // back to the belief that entered the chunk
+      if (t0 == 0 || len == 0) break;
+      mf = m_in;
+      Pf = mat_symmetrize(P_in);
+    }
+    const Vec<double, D> m_next = m_s;
+    const Mat<double, D> P_next = P_s;
+    const Mat<double, D> FP = f_identity ? Pf : mat_mul(F, Pf);                 // F Pf
+    const Mat<double, D> Pp = mat_symmetrize(
+        mat_add(f_identity ? Pf : mat_mul_nt(FP, F), sQ));                      // F Pf F^T + sQ
+    const CholF<double, D> Lp = chol_factor(Pp);
+    const Mat<double, D> Z = chol_solve_mat(Lp, FP);                            // Pp^-1 F Pf = G^T
+    const Vec<double, D> mp = f_identity ? mf : mat_vec(F, mf);
+    Vec<double, D> dm;
+#pragma unroll
+    for (int a = 0; a < D; ++a) dm.a[a] = m_s.a[a] - mp.a[a];
+    const Vec<double, D> Gdm = mat_t_vec(Z, dm);
+#pragma unroll
+    for (int a = 0; a < D; ++a) m_s.a[a] = mf.a[a] + Gdm.a[a];
+    const Mat<double, D> dP = mat_sub(P_s, Pp);
+    P_s = mat_sandwich_tn_plus(Z, dP, Pf);                                      // Pf + G (P' - Pp) G^T
+    step(i, DenseTransition<D>{mf, Pf, FP, Pp, Lp, Z, dm, m_next, P_next, m_s, P_s});
+  }
+}
+
 // K3: exact replay of frames [t0, t0+len).  (m, P): the filtered belief of frame t0-1 (the prior
 // itself when t0 == 0); (eta_s, J_s): what all later frames say about the state at the chunk's
-// last frame.  `filt` is this lane's scratch: len records of D + D*D doubles (filtered mean and
-// covariance), written forwards and read backwards.
+// last frame; filt / fs: this lane's scratch records.
 //
 // EKF (extended filter, PinholeObs): every frame is linearised at the lane's own predicted mean
 // (what the reference's dynamax filter does), the predicted mean replaces the
@@ -340,136 +493,68 @@ EKS_HD void dense_replay_chunk_obs(const Obs& obs, int K, int k, int t0, int len
                                    double* ll_out, double* resid_out, size_t fs = 1) {
   const Vec<double, D> m_in = m;
   const Mat<double, D> P_in = P;
-  // fs: distance in doubles between consecutive fields of the scratch records (1: a lane's records are
-  // contiguous; K: the records of the K keypoints are interleaved field by field, so the lanes of a wave -
-  // consecutive keypoints - read and write whole segments.  Per-lane contiguous records cost the wide
-  // multicam shape 1.28 ms in the replay: every 8-byte access of a wave touched 64 different lines.)
-  constexpr int REC = D + D * D;
+  const bool backward = SCORE || ms != nullptr;
+  double* const rec = backward ? filt : nullptr;
   double ll = 0.0, resid = 0.0;
-  for (int i = 0; i < len; ++i) {
-    const int t = t0 + i;
-    if (t > 0) {
-      if (!f_identity) {
-        m = mat_vec(F, m);
-        P = mat_mul_nt(mat_mul(F, P), F);
-      }
-      P = mat_add(P, sQ);
-    }
-    if constexpr (EKF) {
-      // A non-finite predicted mean (a camera-plane crossing or garbage from a poor linearisation
-      // in an EARLY sweep - the sequential filter never sees it) must not be stored: the next
-      // sweep's elements would be built from NaN and every later prefix poisoned for good.  Such a
-      // frame keeps its old linearisation point and reports an unconverged sweep.
-      double xl[D];
+  if constexpr (EKF) {
+    // A non-finite predicted mean (a camera-plane crossing or garbage from a poor linearisation
+    // in an EARLY sweep - the sequential filter never sees it) must not be stored: the next
+    // sweep's elements would be built from NaN and every later prefix poisoned for good.  Such a
+    // frame keeps its old linearisation point and reports an unconverged sweep.
+    double xl[D];
+    auto relinearise = [&](int i, const Vec<double, D>& mp) -> const double* {
 #pragma unroll
       for (int a = 0; a < D; ++a) {
         const double old = xlin[a + (size_t)i * D];
-        const bool fin = fabs(m.a[a]) <= 1.7e308;          // false for NaN and +-inf
-        xl[a] = fin ? m.a[a] : old;
+        const bool fin = fabs(mp.a[a]) <= 1.7e308;         // false for NaN and +-inf
+        xl[a] = fin ? mp.a[a] : old;
         const double scale = fabs(old) > 1.0 ? fabs(old) : 1.0;
         const double ch = fin ? fabs(xl[a] - old) / scale : 1e300;
         resid = ch > resid ? ch : resid;
         xlin[a + (size_t)i * D] = xl[a];
       }
-      ll += belief_update_obs<D, true>(obs, k, t, xl, m, P);
-    } else if constexpr (SCORE) {
-      ll += belief_update_obs<D, true>(obs, k, t, nullptr, m, P);
-    } else {
-      belief_update_obs<D>(obs, k, t, nullptr, m, P);
-    }
-    if (!SCORE && ms == nullptr) continue;
-    double* rec = filt + (size_t)i * REC * fs;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      rec[a * fs] = m.a[a];
-#pragma unroll
-      for (int b = 0; b < D; ++b) rec[(D + a * D + b) * fs] = P.a[a][b];
-    }
-  }
-  if constexpr (EKF) {
+      return xl;
+    };
+    ll = dense_forward_chunk<D, true>(obs, k, t0, len, F, sQ, f_identity, m, P, rec, fs, relinearise);
     *ll_out = ll;
     *resid_out = resid;
+  } else {
+    ll = dense_forward_chunk<D, SCORE>(obs, k, t0, len, F, sQ, f_identity, m, P, rec, fs);
   }
-  if (!SCORE && ms == nullptr) return;
+  if (!backward) return;
+  Mat<double, D> Qi;                                          // SCORE: (sQ)^-1
+  double score = 0.0;
+  if constexpr (SCORE) Qi = chol_solve_mat(chol_factor(sQ), mat_eye<double, D>());
   auto emit = [&](int i, const Vec<double, D>& mo, const Mat<double, D>& Po) {
     if constexpr (SCORE) return;
     const size_t ko = (size_t)(t0 + i) * K + k;
-#pragma unroll
-    for (int a = 0; a < D; ++a) EKS_STREAM_STORE(ms + ko * D + a, (float)mo.a[a]);
-    if (vs_diag) {
-#pragma unroll
-      for (int a = 0; a < D; ++a) EKS_STREAM_STORE(Vs + ko * D + a, (float)Po.a[a][a]);
-    } else {
-#pragma unroll
-      for (int a = 0; a < D; ++a)
-#pragma unroll
-        for (int b = 0; b < D; ++b) EKS_STREAM_STORE(Vs + (ko * D + a) * D + b, (float)Po.a[a][b]);
-    }
+    dense_store_vec<D>(ms, ko, mo);
+    dense_store_mat<D>(Vs, ko, Po, vs_diag);
   };
-  Vec<double, D> m_s;
-  Mat<double, D> P_s;
-  double logdet;
-  condition_on_info(m, P, eta_s, J_s, m_s, P_s, logdet);      // smoothed last frame of the chunk
-  emit(len - 1, m_s, P_s);
-  Mat<double, D> Qi;                                          // SCORE: (sQ)^-1
-  double score = 0.0;
-  if constexpr (SCORE) {
-    Mat<double, D> eye = mat_zero<double, D>();
+  dense_backward_chunk<D>(
+      t0, len, SCORE ? -1 : 0, F, sQ, f_identity, m_in, P_in, m, P, eta_s, J_s, filt, fs,
+      [&](const Vec<double, D>& m_s, const Mat<double, D>& P_s) { emit(len - 1, m_s, P_s); },
+      [&](int i, const DenseTransition<D>& tr) {
+        if constexpr (SCORE) {
+          const Vec<double, D> Fm = f_identity ? tr.m_s : mat_vec(F, tr.m_s);
+          Vec<double, D> dw;
 #pragma unroll
-    for (int a = 0; a < D; ++a) eye.a[a][a] = 1.0;
-    Qi = chol_solve_mat(chol_factor(sQ), eye);
-  }
-  for (int i = len - 2; i >= (SCORE ? -1 : 0); --i) {
-    Vec<double, D> mf;
-    Mat<double, D> Pf;
-    if (i >= 0) {
-      const double* rec = filt + (size_t)i * REC * fs;
+          for (int a = 0; a < D; ++a) dw.a[a] = tr.m_next.a[a] - Fm.a[a];
+          const Mat<double, D> Cx = mat_mul_tn(tr.Z, tr.P_next);        // Cov(x_i, x_{i+1} | y)
+          const Mat<double, D> FC = f_identity ? Cx : mat_mul(F, Cx);
+          const Mat<double, D> FVF = f_identity ? tr.P_s : mat_mul_nt(mat_mul(F, tr.P_s), F);
+          double tr_q = 0.0;
 #pragma unroll
-      for (int a = 0; a < D; ++a) {
-        mf.a[a] = rec[a * fs];
+          for (int a = 0; a < D; ++a)
 #pragma unroll
-        for (int b = 0; b < D; ++b) Pf.a[a][b] = rec[(D + a * D + b) * fs];
-      }
-    } else {                                                  // SCORE: back to the belief that entered the chunk
-      if (t0 == 0 || len == 0) break;
-      mf = m_in;
-      Pf = mat_symmetrize(P_in);
-    }
-    const Vec<double, D> m_next = m_s;
-    const Mat<double, D> P_next = P_s;
-    const Mat<double, D> FP = f_identity ? Pf : mat_mul(F, Pf);                 // F Pf
-    const Mat<double, D> Pp = mat_symmetrize(
-        mat_add(f_identity ? Pf : mat_mul_nt(FP, F), sQ));                      // F Pf F^T + sQ
-    const Mat<double, D> Z = chol_solve_mat(chol_factor(Pp), FP);                  // Pp^-1 F Pf = G^T
-    const Vec<double, D> mp = f_identity ? mf : mat_vec(F, mf);
-    Vec<double, D> dm;
-#pragma unroll
-    for (int a = 0; a < D; ++a) dm.a[a] = m_s.a[a] - mp.a[a];
-    const Vec<double, D> Gdm = mat_t_vec(Z, dm);
-#pragma unroll
-    for (int a = 0; a < D; ++a) m_s.a[a] = mf.a[a] + Gdm.a[a];
-    // P_s = Pf + G (P_s - Pp) G^T,  G = Z^T
-    const Mat<double, D> dP = mat_sub(P_s, Pp);
-    P_s = mat_sandwich_tn_plus(Z, dP, Pf);
-    if constexpr (SCORE) {
-      const Vec<double, D> Fm = f_identity ? m_s : mat_vec(F, m_s);
-      Vec<double, D> dw;
-#pragma unroll
-      for (int a = 0; a < D; ++a) dw.a[a] = m_next.a[a] - Fm.a[a];
-      const Mat<double, D> Cx = mat_mul_tn(Z, P_next);        // Cov(x_i, x_{i+1} | y)
-      const Mat<double, D> FC = f_identity ? Cx : mat_mul(F, Cx);
-      const Mat<double, D> FVF = f_identity ? P_s : mat_mul_nt(mat_mul(F, P_s), F);
-      double tr = 0.0;
-#pragma unroll
-      for (int a = 0; a < D; ++a)
-#pragma unroll
-        for (int b = 0; b < D; ++b)
-          tr += Qi.a[a][b] * (dw.a[a] * dw.a[b] + P_next.a[a][b] + FVF.a[a][b] - FC.a[a][b] - FC.a[b][a]);
-      score += 0.5 * (tr - (double)D);
-    } else {
-      emit(i, m_s, P_s);
-    }
-  }
+            for (int b = 0; b < D; ++b)
+              tr_q += Qi.a[a][b] *
+                      (dw.a[a] * dw.a[b] + tr.P_next.a[a][b] + FVF.a[a][b] - FC.a[a][b] - FC.a[b][a]);
+          score += 0.5 * (tr_q - (double)D);
+        } else {
+          emit(i, tr.m_s, tr.P_s);
+        }
+      });
   if constexpr (SCORE) {
     *ll_out = ll;
     *resid_out = score;

@@ -17,29 +17,16 @@
 
 namespace eks {
 
-// rts_step (eks_math.hpp) that also returns the step's term of Sw: the expressions of ms and Ps are rts_step's own,
-// in its order, so the smoothed belief carried backwards is bit for bit the smoother's.  On entry (ms, Ps) is the
-// smoothed belief on x_{t+1}, on exit on x_t.
+// rts_step (eks_math.hpp) that also returns the step's term of Sw: the same rts_gain and rts_advance, so the smoothed
+// belief carried backwards is bit for bit the smoother's.  On entry (ms, Ps) is the smoothed belief on x_{t+1}, on
+// exit on x_t.
 template <typename R, bool UNIT>
 EKS_HD R rts_step_em(R& ms, R& Ps, R mf, R Pf, const ChainParams<R>& p) {
-  const R Pp = UNIT ? (Pf + p.q_s) : (p.times_a2(Pf) + p.q_s);
-  const R ig = rcp(Pp);
-  const R h = p.q_s * ig;
-  const R G = UNIT ? Pf * ig : p.a * Pf * ig;
-  const R amf = UNIT ? mf : p.times_a(mf);
-  const R g = UNIT ? h : (h - p.oma) * rcp(p.a);
-  const R ew = h * (ms - amf);
+  const RtsGain<R> k = rts_gain<R, UNIT>(mf, Pf, p);
+  const R ew = k.h * (ms - k.amf);
   const R a2Pf = UNIT ? Pf : p.times_a2(Pf);
-  const R term = ew * ew + (h * h * Ps + a2Pf * h);
-  ms = mf + G * (ms - amf);
-  const R Ps_prod = Pf * h + G * G * Ps;
-#ifdef EKS_RTS_PRODUCT_ONLY
-  (void)g;
-  Ps = Ps_prod;
-#else
-  const R Ps_dev = Ps + (Pf * h - g * (R(2) - g) * Ps);
-  Ps = (g < R(0.25) && g > R(-0.25)) ? Ps_dev : Ps_prod;
-#endif
+  const R term = ew * ew + (k.h * k.h * Ps + a2Pf * k.h);
+  rts_advance(ms, Ps, mf, Pf, k);
   return term;
 }
 
@@ -84,9 +71,10 @@ EKS_HD void em_replay_lane(const SampleWs& W, const DiagModel& M, const EmCall& 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// General (D, O) models, float64 throughout.  dense_increments_chunk's loops - the exact filter over the chunk into
-// the lane's scratch records, then backwards to i = -1, so the transition between the chunk's first frame and the
-// frame before it belongs to THIS chunk, from the belief that entered it.  With Z = Pp^-1 F Pf (G = Z^T),
+// General (D, O) models, float64 throughout.  dense_increments_chunk's passes (eks_dense_lane.hpp: dense_forward_chunk,
+// dense_backward_chunk) - the exact filter over the chunk into the lane's scratch records, then backwards to i = -1,
+// so the transition between the chunk's first frame and the frame before it belongs to THIS chunk, from the belief
+// that entered it.  With Z = Pp^-1 F Pf (G = Z^T),
 // H = sQ Pp^-1 formed as H^T = Pp^-1 (sQ), and (m', P') the smoothed belief of frame t+1:
 //     E[w_t | y]   = H (m' - F mf)
 //     Cov(w_t | y) = H P' H^T + F (Pf - Z^T F Pf) F^T
@@ -101,69 +89,22 @@ EKS_HD void dense_em_chunk(const Obs& obs, int k, int t0, int len, const Mat<dou
                            bool diag) {
   const Vec<double, D> m_in = m;
   const Mat<double, D> P_in = P;
-  constexpr int REC = D + D * D;
-  for (int i = 0; i < len; ++i) {
-    const int t = t0 + i;
-    if (t > 0) {
-      if (!f_identity) {
-        m = mat_vec(F, m);
-        P = mat_mul_nt(mat_mul(F, P), F);
-      }
-      P = mat_add(P, sQ);
-    }
-    belief_update_obs<D>(obs, k, t, nullptr, m, P);
-    double* rec = filt + (size_t)i * REC * fs;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      rec[a * fs] = m.a[a];
-#pragma unroll
-      for (int b = 0; b < D; ++b) rec[(D + a * D + b) * fs] = P.a[a][b];
-    }
-  }
-  Vec<double, D> m_s;
-  Mat<double, D> P_s;
-  double logdet;
-  condition_on_info(m, P, eta_s, J_s, m_s, P_s, logdet);      // smoothed last frame of the chunk
+  dense_forward_chunk<D, false>(obs, k, t0, len, F, sQ, f_identity, m, P, filt, fs);
   Mat<double, D> Sw = mat_zero<double, D>();
-  for (int i = len - 2; i >= -1; --i) {
-    Vec<double, D> mf;
-    Mat<double, D> Pf;
-    if (i >= 0) {
-      const double* rec = filt + (size_t)i * REC * fs;
+  dense_backward_chunk<D>(
+      t0, len, -1, F, sQ, f_identity, m_in, P_in, m, P, eta_s, J_s, filt, fs,
+      [](const Vec<double, D>&, const Mat<double, D>&) {},
+      [&](int, const DenseTransition<D>& tr) {
+        const Mat<double, D> Ht = chol_solve_mat(tr.Lp, sQ);                        // Pp^-1 sQ = H^T
+        const Vec<double, D> ew = mat_t_vec(Ht, tr.dm);                             // H (m' - F mf)
+        const Mat<double, D> Wm = mat_sub(tr.Pf, mat_mul_tn(tr.Z, tr.FP));          // Pf - G Pp G^T
+        const Mat<double, D> FWF = f_identity ? Wm : mat_mul_nt(mat_mul(F, Wm), F);
+        const Mat<double, D> cw = mat_sandwich_tn_plus(Ht, tr.P_next, FWF);         // H P' H^T + F W F^T
 #pragma unroll
-      for (int a = 0; a < D; ++a) {
-        mf.a[a] = rec[a * fs];
+        for (int a = 0; a < D; ++a)
 #pragma unroll
-        for (int b = 0; b < D; ++b) Pf.a[a][b] = rec[(D + a * D + b) * fs];
-      }
-    } else {                                                  // back to the belief that entered the chunk
-      if (t0 == 0) break;
-      mf = m_in;
-      Pf = mat_symmetrize(P_in);
-    }
-    const Mat<double, D> P_next = P_s;
-    const Mat<double, D> FP = f_identity ? Pf : mat_mul(F, Pf);                 // F Pf
-    const Mat<double, D> Pp = mat_symmetrize(mat_add(f_identity ? Pf : mat_mul_nt(FP, F), sQ));
-    const CholF<double, D> Lp = chol_factor(Pp);
-    const Mat<double, D> Z = chol_solve_mat(Lp, FP);                            // Pp^-1 F Pf = G^T
-    const Mat<double, D> Ht = chol_solve_mat(Lp, sQ);                           // Pp^-1 sQ = H^T
-    const Vec<double, D> mp = f_identity ? mf : mat_vec(F, mf);
-    Vec<double, D> dm;
-#pragma unroll
-    for (int a = 0; a < D; ++a) dm.a[a] = m_s.a[a] - mp.a[a];
-    const Vec<double, D> ew = mat_t_vec(Ht, dm);                                // H (m' - F mf)
-    const Mat<double, D> Wm = mat_sub(Pf, mat_mul_tn(Z, FP));                   // Pf - G Pp G^T
-    const Mat<double, D> FWF = f_identity ? Wm : mat_mul_nt(mat_mul(F, Wm), F);
-    const Mat<double, D> cw = mat_sandwich_tn_plus(Ht, P_next, FWF);            // H P' H^T + F W F^T
-#pragma unroll
-    for (int a = 0; a < D; ++a)
-#pragma unroll
-      for (int b = 0; b < D; ++b) Sw.a[a][b] += ew.a[a] * ew.a[b] + cw.a[a][b];
-    const Vec<double, D> Gdm = mat_t_vec(Z, dm);                                // the smoother's own step
-#pragma unroll
-    for (int a = 0; a < D; ++a) m_s.a[a] = mf.a[a] + Gdm.a[a];
-    P_s = mat_sandwich_tn_plus(Z, mat_sub(P_s, Pp), Pf);                        // Pf + G (P' - Pp) G^T
-  }
+          for (int b = 0; b < D; ++b) Sw.a[a][b] += ew.a[a] * ew.a[b] + cw.a[a][b];
+      });
   if (diag) {
 #pragma unroll
     for (int a = 0; a < D; ++a) part[a] = Sw.a[a][a];

@@ -18,29 +18,16 @@
 
 namespace eks {
 
-// rts_step (eks_math.hpp) with the three increment outputs: the expressions of ms and Ps are rts_step's own, in its
-// order, so both agree bit for bit with smooth_rows on the same inputs.  On entry (ms, Ps) is the smoothed belief on
-// x_{t+1}, on exit on x_t.
+// rts_step (eks_math.hpp) with the three increment outputs: the same rts_gain and rts_advance, so ms and Ps agree bit
+// for bit with smooth_rows on the same inputs.  On entry (ms, Ps) is the smoothed belief on x_{t+1}, on exit on x_t.
 template <typename R, bool UNIT>
 EKS_HD void rts_step_increments(R& ms, R& Ps, R mf, R Pf, const ChainParams<R>& p, R& lag1, R& dmean, R& dV) {
-  const R Pp = UNIT ? (Pf + p.q_s) : (p.times_a2(Pf) + p.q_s);
-  const R ig = rcp(Pp);
-  const R h = p.q_s * ig;
-  const R G = UNIT ? Pf * ig : p.a * Pf * ig;
-  const R amf = UNIT ? mf : p.times_a(mf);
-  const R g = UNIT ? h : (h - p.oma) * rcp(p.a);
-  const R dev = ms - amf;
-  lag1 = G * Ps;
-  dmean = UNIT ? g * dev : g * dev - p.oma * mf;
-  dV = g * g * Ps + Pf * h;
-  ms = mf + G * (ms - amf);
-  const R Ps_prod = Pf * h + G * G * Ps;
-#ifdef EKS_RTS_PRODUCT_ONLY
-  Ps = Ps_prod;
-#else
-  const R Ps_dev = Ps + (Pf * h - g * (R(2) - g) * Ps);
-  Ps = (g < R(0.25) && g > R(-0.25)) ? Ps_dev : Ps_prod;
-#endif
+  const RtsGain<R> k = rts_gain<R, UNIT>(mf, Pf, p);
+  const R dev = ms - k.amf;
+  lag1 = k.G * Ps;
+  dmean = UNIT ? k.g * dev : k.g * dev - p.oma * mf;
+  dV = k.g * k.g * Ps + Pf * k.h;
+  rts_advance(ms, Ps, mf, Pf, k);
 }
 
 // RTS pass backwards over the filtered chunk (v0, v1) = (mf, Pf) from the smoothed belief (m, P) on the frame after it;
@@ -102,10 +89,10 @@ EKS_HD void increments_replay_lane(const SampleWs& W, const DiagModel& M, const 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// General (D, O) models, float64 in the lane, one rounding to float32 at the store.  dense_replay_chunk_obs's linear
-// branch with three more outputs per transition; the backward loop runs to i = -1 like its SCORE branch, so the
-// transition between the chunk's first frame and the frame before it is emitted by THIS chunk, from the belief that
-// entered it.  With Z = Pp^-1 F Pf (G = Z^T), (m', P') the smoothed belief of frame t+1:
+// General (D, O) models, float64 in the lane, one rounding to float32 at the store.  The chunk's forward pass and
+// backward walker (eks_dense_lane.hpp: dense_forward_chunk, dense_backward_chunk) with three more outputs per
+// transition; the walk runs to i = -1 like the SCORE form, so the transition between the chunk's first frame and the
+// frame before it is emitted by THIS chunk, from the belief that entered it.  With Z = Pp^-1 F Pf (G = Z^T), (m', P') the smoothed belief of frame t+1:
 //     lag1  = G P'                   (row: coordinate of x_t, column: of x_{t+1})
 //     dmean = m' - m_t
 //     dV    = (I - G) P' (I - G)^T + (Pf - G Pp G^T),      G Pp G^T = Z^T (F Pf)
@@ -117,26 +104,6 @@ struct DenseIncrementsOut {
   int T;
 };
 
-template <int D>
-EKS_HD void dense_store_vec(float* dst, size_t ko, const Vec<double, D>& v) {
-  if (!dst) return;
-#pragma unroll
-  for (int a = 0; a < D; ++a) EKS_STREAM_STORE(dst + ko * D + a, (float)v.a[a]);
-}
-template <int D>
-EKS_HD void dense_store_mat(float* dst, size_t ko, const Mat<double, D>& P, bool diag) {
-  if (!dst) return;
-  if (diag) {
-#pragma unroll
-    for (int a = 0; a < D; ++a) EKS_STREAM_STORE(dst + ko * D + a, (float)P.a[a][a]);
-  } else {
-#pragma unroll
-    for (int a = 0; a < D; ++a)
-#pragma unroll
-      for (int b = 0; b < D; ++b) EKS_STREAM_STORE(dst + (ko * D + a) * D + b, (float)P.a[a][b]);
-  }
-}
-
 // (m, P): the filtered belief of frame t0 - 1 (the prior itself when t0 == 0); (eta_s, J_s): what all later frames say
 // about the state at the chunk's last frame; filt / fs: this lane's scratch records as in dense_replay_chunk_obs.
 template <int D, typename Obs>
@@ -146,87 +113,38 @@ EKS_HD void dense_increments_chunk(const Obs& obs, int K, int k, int t0, int len
                                    const DenseIncrementsOut& out, size_t fs) {
   const Vec<double, D> m_in = m;
   const Mat<double, D> P_in = P;
-  constexpr int REC = D + D * D;
-  for (int i = 0; i < len; ++i) {
-    const int t = t0 + i;
-    if (t > 0) {
-      if (!f_identity) {
-        m = mat_vec(F, m);
-        P = mat_mul_nt(mat_mul(F, P), F);
-      }
-      P = mat_add(P, sQ);
-    }
-    belief_update_obs<D>(obs, k, t, nullptr, m, P);
-    double* rec = filt + (size_t)i * REC * fs;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      rec[a * fs] = m.a[a];
-#pragma unroll
-      for (int b = 0; b < D; ++b) rec[(D + a * D + b) * fs] = P.a[a][b];
-    }
-  }
-  Vec<double, D> m_s;
-  Mat<double, D> P_s;
-  double logdet;
-  condition_on_info(m, P, eta_s, J_s, m_s, P_s, logdet);      // smoothed last frame of the chunk
-  {
-    const size_t ko = (size_t)(t0 + len - 1) * K + k;
-    dense_store_vec<D>(out.ms, ko, m_s);
-    dense_store_mat<D>(out.Vs, ko, P_s, out.vs_diag);
-    if (t0 + len == out.T) {                                  // row T-1 of the increment outputs: zeros
-      dense_store_vec<D>(out.dmean, ko, vec_zero<double, D>());
-      dense_store_mat<D>(out.lag1, ko, mat_zero<double, D>(), out.vs_diag);
-      dense_store_mat<D>(out.dV, ko, mat_zero<double, D>(), out.vs_diag);
-    }
-  }
+  dense_forward_chunk<D, false>(obs, k, t0, len, F, sQ, f_identity, m, P, filt, fs);
   const Mat<double, D> eye = mat_eye<double, D>();
-  for (int i = len - 2; i >= -1; --i) {
-    Vec<double, D> mf;
-    Mat<double, D> Pf;
-    if (i >= 0) {
-      const double* rec = filt + (size_t)i * REC * fs;
+  dense_backward_chunk<D>(
+      t0, len, -1, F, sQ, f_identity, m_in, P_in, m, P, eta_s, J_s, filt, fs,
+      [&](const Vec<double, D>& m_s, const Mat<double, D>& P_s) {
+        const size_t ko = (size_t)(t0 + len - 1) * K + k;
+        dense_store_vec<D>(out.ms, ko, m_s);
+        dense_store_mat<D>(out.Vs, ko, P_s, out.vs_diag);
+        if (t0 + len == out.T) {                                  // row T-1 of the increment outputs: zeros
+          dense_store_vec<D>(out.dmean, ko, vec_zero<double, D>());
+          dense_store_mat<D>(out.lag1, ko, mat_zero<double, D>(), out.vs_diag);
+          dense_store_mat<D>(out.dV, ko, mat_zero<double, D>(), out.vs_diag);
+        }
+      },
+      [&](int i, const DenseTransition<D>& tr) {
+        const size_t ko = (size_t)(t0 + i) * K + k;
+        if (i >= 0) {
+          dense_store_vec<D>(out.ms, ko, tr.m_s);
+          dense_store_mat<D>(out.Vs, ko, tr.P_s, out.vs_diag);
+        }
+        if (out.dmean) {
+          Vec<double, D> inc;
 #pragma unroll
-      for (int a = 0; a < D; ++a) {
-        mf.a[a] = rec[a * fs];
-#pragma unroll
-        for (int b = 0; b < D; ++b) Pf.a[a][b] = rec[(D + a * D + b) * fs];
-      }
-    } else {                                                  // back to the belief that entered the chunk
-      if (t0 == 0) break;
-      mf = m_in;
-      Pf = mat_symmetrize(P_in);
-    }
-    const Vec<double, D> m_next = m_s;
-    const Mat<double, D> P_next = P_s;
-    const Mat<double, D> FP = f_identity ? Pf : mat_mul(F, Pf);                 // F Pf
-    const Mat<double, D> Pp = mat_symmetrize(mat_add(f_identity ? Pf : mat_mul_nt(FP, F), sQ));
-    const Mat<double, D> Z = chol_solve_mat(chol_factor(Pp), FP);               // Pp^-1 F Pf = G^T
-    const Vec<double, D> mp = f_identity ? mf : mat_vec(F, mf);
-    Vec<double, D> dm;
-#pragma unroll
-    for (int a = 0; a < D; ++a) dm.a[a] = m_s.a[a] - mp.a[a];
-    const Vec<double, D> Gdm = mat_t_vec(Z, dm);
-#pragma unroll
-    for (int a = 0; a < D; ++a) m_s.a[a] = mf.a[a] + Gdm.a[a];
-    const Mat<double, D> dP = mat_sub(P_s, Pp);
-    P_s = mat_sandwich_tn_plus(Z, dP, Pf);                                      // Pf + G (P' - Pp) G^T
-    const size_t ko = (size_t)(t0 + i) * K + k;
-    if (i >= 0) {
-      dense_store_vec<D>(out.ms, ko, m_s);
-      dense_store_mat<D>(out.Vs, ko, P_s, out.vs_diag);
-    }
-    if (out.dmean) {
-      Vec<double, D> inc;
-#pragma unroll
-      for (int a = 0; a < D; ++a) inc.a[a] = m_next.a[a] - m_s.a[a];
-      dense_store_vec<D>(out.dmean, ko, inc);
-    }
-    if (out.lag1) dense_store_mat<D>(out.lag1, ko, mat_mul_tn(Z, P_next), out.vs_diag);   // Cov(x_i, x_{i+1} | y)
-    if (out.dV) {
-      const Mat<double, D> W = mat_sub(Pf, mat_mul_tn(Z, FP));                  // Pf - G Pp G^T
-      dense_store_mat<D>(out.dV, ko, mat_sandwich_tn_plus(mat_sub(eye, Z), P_next, W), out.vs_diag);
-    }
-  }
+          for (int a = 0; a < D; ++a) inc.a[a] = tr.m_next.a[a] - tr.m_s.a[a];
+          dense_store_vec<D>(out.dmean, ko, inc);
+        }
+        if (out.lag1) dense_store_mat<D>(out.lag1, ko, mat_mul_tn(tr.Z, tr.P_next), out.vs_diag);   // Cov(x_i, x_{i+1} | y)
+        if (out.dV) {
+          const Mat<double, D> W = mat_sub(tr.Pf, mat_mul_tn(tr.Z, tr.FP));     // Pf - G Pp G^T
+          dense_store_mat<D>(out.dV, ko, mat_sandwich_tn_plus(mat_sub(eye, tr.Z), tr.P_next, W), out.vs_diag);
+        }
+      });
 }
 
 }  // namespace eks

@@ -103,8 +103,8 @@ EKS_HD void innov_replay_lane(const SampleWs& W, const DiagModel& M, const Innov
 // ------------------------------------------------------------------------------------------------------------------
 // General (D, O) models, float64 in the lane, one rounding to float32 at the store.  (m, P) enters as the FILTERED
 // belief of frame t0 - 1 (the prior itself when t0 == 0), as in dense_em_chunk; per frame: predict, the marginal
-// innovations of all O rows from the predicted belief, then belief_update_obs's loop - its expressions, in its
-// order - with the sums of log sigma and d^2 / sigma kept.  No scratch records and nothing is factored: a singular Q
+// innovations of all O rows from the predicted belief, then the update itself (belief_update_obs_acc) with the sums
+// of log sigma and d^2 / sigma kept.  No scratch records and nothing is factored: a singular Q
 // or S0 is fine while the innovation variances are positive.  Returns the chunk's log-likelihood.
 // ------------------------------------------------------------------------------------------------------------------
 struct DenseInnovOut {
@@ -119,13 +119,7 @@ EKS_HD double dense_innov_chunk(const Obs& obs, int K, int O, int k, int t0, int
   double acc = 0.0;
   for (int i = 0; i < len; ++i) {
     const int t = t0 + i;
-    if (t > 0) {
-      if (!f_identity) {
-        m = mat_vec(F, m);
-        P = mat_mul_nt(mat_mul(F, P), F);
-      }
-      P = mat_add(P, sQ);
-    }
+    if (t > 0) dense_predict(F, sQ, f_identity, m, P);
     const size_t fk = (size_t)t * K + k;
     if (out.innov || out.innov_var) {
       size_t at = fk * O;
@@ -136,24 +130,9 @@ EKS_HD double dense_innov_chunk(const Obs& obs, int K, int O, int k, int t0, int
       });
     }
     double sum_log = 0.0, sum_sq = 0.0;
-    obs.visit(t, k, nullptr, [&](const Vec<double, D>& h, double yv, double r) {
-      const Vec<double, D> u = mat_vec(P, h);
-      const double sigma = r + dot(h, u);
-      const double g = rcp(sigma);
-      const double d = yv - dot(h, m), gd = g * d;
+    belief_update_obs_acc<D>(obs, k, t, nullptr, m, P, [&](double sigma, double d, double gd) {
       sum_log += log(sigma);
       sum_sq += d * gd;
-#pragma unroll
-      for (int a = 0; a < D; ++a) {
-        m.a[a] += u.a[a] * gd;
-        const double ug = u.a[a] * g;
-#pragma unroll
-        for (int b = a; b < D; ++b) {
-          const double pv = P.a[a][b] - ug * u.a[b];
-          P.a[a][b] = pv;
-          P.a[b][a] = pv;
-        }
-      }
     });
     const double ll = -0.5 * ((double)O * kLog2Pi + sum_log + sum_sq);
     if (out.nis) EKS_STREAM_STORE(out.nis + fk, (float)sum_sq);

@@ -183,23 +183,41 @@ EKS_HD void fuse_info(R& m, R& P, R eta, R J) {
 // rounded once from float64: ChainParams::oma); elsewhere (|g| >= 1/4: light smoothing, or a frame in front of an
 // occluded one whose Ps_{t+1} dwarfs Pf, where the deviation form would cancel) the products of non-negative terms of
 // rounds 1-5 stand.  Per lane, by select.
+// The step is two pieces, shared by every scalar-chain kernel that walks backwards: the gains of frame t from its
+// filtered belief (rts_gain), and the advance of (ms, Ps) with them (rts_advance: the one place the select lives).
+template <typename R>
+struct RtsGain {
+  R h, G, g, amf;
+};
+
 template <typename R, bool UNIT>
-EKS_HD void rts_step(R& ms, R& Ps, R mf, R Pf, const ChainParams<R>& p) {
+EKS_HD RtsGain<R> rts_gain(R mf, R Pf, const ChainParams<R>& p) {
   const R Pp = UNIT ? (Pf + p.q_s) : (p.times_a2(Pf) + p.q_s);
   const R ig = rcp(Pp);
   const R h = p.q_s * ig;
   const R G = UNIT ? Pf * ig : p.a * Pf * ig;
   const R amf = UNIT ? mf : p.times_a(mf);
   const R g = UNIT ? h : (h - p.oma) * rcp(p.a);
-  ms = mf + G * (ms - amf);                // (the mean is not divided by 1 - G^2: its product form holds 1e-6 everywhere)
-  const R Ps_prod = Pf * h + G * G * Ps;
+  return RtsGain<R>{h, G, g, amf};
+}
+
+// (ms, Ps) from frame t+1 to frame t with the gains k of frame t: the mean update and the product / deviation select.
+// rts_step, rts_step_increments (eks_increments_lane.hpp) and rts_step_em (eks_em_lane.hpp) all advance through here.
+template <typename R>
+EKS_HD void rts_advance(R& ms, R& Ps, R mf, R Pf, const RtsGain<R>& k) {
+  ms = mf + k.G * (ms - k.amf);            // (the mean is not divided by 1 - G^2: its product form holds 1e-6 everywhere)
+  const R Ps_prod = Pf * k.h + k.G * k.G * Ps;
 #ifdef EKS_RTS_PRODUCT_ONLY                 // (A/B builds: rounds 1-5's step)
-  (void)g;
   Ps = Ps_prod;
 #else
-  const R Ps_dev = Ps + (Pf * h - g * (R(2) - g) * Ps);
-  Ps = (g < R(0.25) && g > R(-0.25)) ? Ps_dev : Ps_prod;
+  const R Ps_dev = Ps + (Pf * k.h - k.g * (R(2) - k.g) * Ps);
+  Ps = (k.g < R(0.25) && k.g > R(-0.25)) ? Ps_dev : Ps_prod;
 #endif
+}
+
+template <typename R, bool UNIT>
+EKS_HD void rts_step(R& ms, R& Ps, R mf, R Pf, const ChainParams<R>& p) {
+  rts_advance(ms, Ps, mf, Pf, rts_gain<R, UNIT>(mf, Pf, p));
 }
 
 }  // namespace eks

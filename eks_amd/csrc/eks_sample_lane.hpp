@@ -97,6 +97,8 @@ EKS_HD void filter_var_loaded(float (&v1)[B], int len, const ChainParams<float>&
 }
 
 // (G_t, sd_t) of one frame from its filtered variance; `last`: t == T - 1 (nothing to condition on).
+// (Pp, h, G as in rts_gain, eks_math.hpp; kept apart from it: taken from rts_gain the sampler's kernels come out of
+// the compiler as different code.)
 template <bool UNIT>
 EKS_HD void sample_coeffs(float Pf, const ChainParams<float>& p, bool last, float& G, float& sd) {
   const float Pp = UNIT ? (Pf + p.q_s) : (p.times_a2(Pf) + p.q_s);
