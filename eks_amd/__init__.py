@@ -24,6 +24,8 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'process_noise_statistics': 'em', 'refine_smooth_param_em': 'em', 'fit_process_noise_em': 'em',
         'filter_innovations': 'diagnostics', 'log_likelihood': 'diagnostics', 'innovation_summary': 'diagnostics',
         'innovations_singlecam': 'diagnostics',
+        'process_noise_scale_from_times': 'irregular', 'smooth_time_varying': 'irregular',
+        'smooth_singlecam_irregular': 'irregular',
     }
     if name in table:
         return getattr(importlib.import_module(f'.{table[name]}', __name__), name)

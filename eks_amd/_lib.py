@@ -32,6 +32,9 @@ SIGNATURES = {
     'eks_status_string': (c_char_p, [ctypes.c_int]),
     'eks_smooth_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
     'eks_smooth': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
+    'eks_smooth_tv_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
+    'eks_smooth_tv': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 3 + [c_int32] + [c_void_p] * 9
+                      + [c_size_t, c_void_p]),
     'eks_smooth_increments_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
     'eks_smooth_increments': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 14 + [c_size_t, c_void_p]),
     'eks_em_stats_workspace_bytes': (c_size_t, [POINTER(EksDims)]),

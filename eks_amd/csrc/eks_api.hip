@@ -62,6 +62,39 @@ int eks_smooth(const eks_dims_t* d, const float* y, const float* var, const doub
   return dense_smooth(*d, y, var, M, ms, Vs, workspace, workspace_bytes, st);
 }
 
+// shapes eks_smooth_tv takes (EKS_OK) or the status it refuses them with; nothing here touches the device
+static int smooth_tv_check(const eks_dims_t* d) {
+  const int rc = check_dims(d);
+  if (rc != EKS_OK) return rc;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_smooth_tv_check(*d);
+  if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
+  return dense_smooth_tv_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim) ? EKS_OK : EKS_ERR_SHAPE;
+}
+
+size_t eks_smooth_tv_workspace_bytes(const eks_dims_t* d) {
+  if (smooth_tv_check(d) != EKS_OK) return 0;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_em_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
+  return dense_smooth_tv_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+}
+
+int eks_smooth_tv(const eks_dims_t* d, const float* y, const float* var, const float* qscale,
+                  int32_t qscale_per_keypoint, const double* m0, const double* S0, const double* A, const double* C,
+                  const double* Q, const double* s, float* ms, float* Vs, void* workspace, size_t workspace_bytes,
+                  eks_stream_t stream) {
+  const int rc = smooth_tv_check(d);
+  if (rc != EKS_OK) return rc;
+  if (!y || !var || !qscale || !m0 || !S0 || !A || !C || !Q || !s || !ms || !Vs) return EKS_ERR_NULL;
+  if (!workspace) return EKS_ERR_WORKSPACE;
+  if (workspace_bytes < eks_smooth_tv_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (d->flags & EKS_FLAG_DIAG_MODEL) {
+    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
+    return diag_smooth_tv(*d, y, var, qscale, qscale_per_keypoint, M, ms, Vs, workspace, workspace_bytes, st);
+  }
+  const DenseModel M{m0, S0, A, C, Q, s};
+  return dense_smooth_tv(*d, y, var, qscale, qscale_per_keypoint, M, ms, Vs, workspace, workspace_bytes, st);
+}
+
 // shapes eks_smooth_increments takes (EKS_OK) or the status it refuses them with; nothing here touches the device
 static int increments_check(const eks_dims_t* d) {
   const int rc = check_dims(d);

@@ -20,6 +20,7 @@
 #include "eks_increments_lane.hpp"
 #include "eks_innov_lane.hpp"
 #include "eks_internal.hpp"
+#include "eks_smooth_tv_lane.hpp"
 
 namespace eks {
 
@@ -468,6 +469,94 @@ int dense_increments(const eks_dims_t& d, const float* y, const float* var, cons
       hipLaunchKernelGGL((dense_increments_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
                          Mm.s, obs, L.pre, L.suf, L.bprior, L.bsuffix, L.filt, out);
     }
+  })
+  return hip_status(hipGetLastError());
+}
+
+// ---- eks_smooth_tv on general models: the generic organisation with w_t s Q per frame --------------------------------
+// Summarize and replay of their own (eks_smooth_tv_lane.hpp: dense_tv_element, dense_tv_replay_chunk) around
+// dense_scan -> dense_scan_blocks as they are - the scan composes elements and never sees Q.  Always the generic kernels
+// and their workspace layout, whatever dense_path would pick for eks_smooth: correct first, like the dense sampler.
+template <int D>
+__global__ __launch_bounds__(64) void dense_tv_summarize_kernel(DenseGeom G, DenseModelPtrs M,
+                                                               const double* __restrict__ s, LinearObs<D> obs,
+                                                               const float* __restrict__ qscale, int per_keypoint,
+                                                               double* __restrict__ elems, double* __restrict__ first) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.ncs) return;
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  const DenseNoiseScale ns = per_keypoint ? DenseNoiseScale{qscale, G.K, k} : DenseNoiseScale{qscale, 1, 0};
+  const int t0 = j * G.Bs, len = min(G.Bs, G.T - t0);
+  const DElem<double, D> e = dense_tv_element<D>(obs, ns, k, t0, len, F, sQ, fid);
+  store_delem<double, D>(elems + (size_t)idx * delem_doubles<D>(), e);
+  if (j == 0) {   // the belief the scan starts from: the prior updated with frame 0 (no predict, no w)
+    Vec<double, D> m;
+    Mat<double, D> P;
+    load_prior<D>(M, k, m, P);
+    belief_update_obs<D>(obs, k, 0, nullptr, m, P);
+    dense_store_rec<D>(first + (size_t)k * (D + D * D), 1, m, P);
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(64) void dense_tv_replay_kernel(DenseGeom G, DenseModelPtrs M,
+                                                            const double* __restrict__ s, LinearObs<D> obs,
+                                                            const float* __restrict__ qscale, int per_keypoint,
+                                                            const double* __restrict__ pre,
+                                                            const double* __restrict__ suf,
+                                                            const double* __restrict__ bprior,
+                                                            const double* __restrict__ bsuffix,
+                                                            double* __restrict__ filt, float* __restrict__ ms,
+                                                            float* __restrict__ Vs, int vs_diag) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.nc) return;
+  constexpr int REC = D + D * D;
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  const DenseNoiseScale ns = per_keypoint ? DenseNoiseScale{qscale, G.K, k} : DenseNoiseScale{qscale, 1, 0};
+  Vec<double, D> m, eta;
+  Mat<double, D> P, J;
+  dense_chunk_boundary<D>(G, M, k, j, j, pre, suf, bprior, bsuffix, m, P, eta, J);   // one element per lane (Bs == B)
+  const int t0 = j * G.B, len = min(G.B, G.T - t0);
+  dense_tv_replay_chunk<D>(obs, ns, G.K, k, t0, len, F, sQ, fid, m, P, eta, J, filt + (size_t)t0 * REC * G.K + k, ms, Vs,
+                           vs_diag != 0, (size_t)G.K);
+}
+
+size_t dense_smooth_tv_workspace_bytes(int T, int K, int D, int O) {
+  return dense_increments_workspace_bytes(T, K, D, O);   // the generic layout, with the same launch-index check
+}
+
+int dense_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
+                    const DenseModel& Mm, float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
+  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
+  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
+  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
+  if (ws_bytes < dense_smooth_tv_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
+  const int lanes = K * G.nc;
+  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
+  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
+  const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0, pk = per_keypoint ? 1 : 0;
+  const Gate open{nullptr, 0.0};
+  EKS_DISPATCH_D(D, {
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
+    {
+      ProfScope ps("dense_tv_summarize", st);
+      hipLaunchKernelGGL(dense_tv_summarize_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs, qscale,
+                         pk, L.elems, L.first);
+    }
+    {
+      ProfScope ps("dense_tv_scan", st);
+      dense_scan_launch<DD>(G, L, open, st);
+    }
+    ProfScope ps("dense_tv_replay", st);
+    hipLaunchKernelGGL(dense_tv_replay_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs, qscale, pk,
+                       L.pre, L.suf, L.bprior, L.bsuffix, L.filt, ms, Vs, vs_diag);
   })
   return hip_status(hipGetLastError());
 }

@@ -428,12 +428,14 @@ struct DenseTransition {
 // its state.  last(m_s, P_s) receives the smoothed last frame, step(i, tr) every transition from i = len-2 down to
 // i_end: 0, or -1 to include the transition out of the belief (m_in, P_in) that entered the chunk (there is none
 // when t0 == 0).  Only Pp is factored, never Q: singular Q or S0 are fine while Pp is positive definite.
-template <int D, typename Last, typename Step>
-EKS_HD void dense_backward_chunk(int t0, int len, int i_end, const Mat<double, D>& F, const Mat<double, D>& sQ,
-                                 bool f_identity, const Vec<double, D>& m_in, const Mat<double, D>& P_in,
-                                 const Vec<double, D>& m, const Mat<double, D>& P, const Vec<double, D>& eta_s,
-                                 const Mat<double, D>& J_s, const double* __restrict__ filt, size_t fs, Last&& last,
-                                 Step&& step) {
+// sq_at(i): the process noise of the transition from frame i to frame i+1 of the chunk (dense_backward_chunk: the
+// same s Q everywhere; eks_smooth_tv_lane.hpp: w_{t0+i+1} s Q).
+template <int D, typename NoiseAt, typename Last, typename Step>
+EKS_HD void dense_backward_walk(int t0, int len, int i_end, const Mat<double, D>& F, NoiseAt&& sq_at,
+                                bool f_identity, const Vec<double, D>& m_in, const Mat<double, D>& P_in,
+                                const Vec<double, D>& m, const Mat<double, D>& P, const Vec<double, D>& eta_s,
+                                const Mat<double, D>& J_s, const double* __restrict__ filt, size_t fs, Last&& last,
+                                Step&& step) {
   constexpr int REC = D + D * D;
   Vec<double, D> m_s;
   Mat<double, D> P_s;
@@ -454,7 +456,7 @@ EKS_HD void dense_backward_chunk(int t0, int len, int i_end, const Mat<double, D
     const Mat<double, D> P_next = P_s;
     const Mat<double, D> FP = f_identity ? Pf : mat_mul(F, Pf);                 // F Pf
     const Mat<double, D> Pp = mat_symmetrize(
-        mat_add(f_identity ? Pf : mat_mul_nt(FP, F), sQ));                      // F Pf F^T + sQ
+        mat_add(f_identity ? Pf : mat_mul_nt(FP, F), sq_at(i)));                // F Pf F^T + sQ
     const CholF<double, D> Lp = chol_factor(Pp);
     const Mat<double, D> Z = chol_solve_mat(Lp, FP);                            // Pp^-1 F Pf = G^T
     const Vec<double, D> mp = f_identity ? mf : mat_vec(F, mf);
@@ -468,6 +470,17 @@ EKS_HD void dense_backward_chunk(int t0, int len, int i_end, const Mat<double, D
     P_s = mat_sandwich_tn_plus(Z, dP, Pf);                                      // Pf + G (P' - Pp) G^T
     step(i, DenseTransition<D>{mf, Pf, FP, Pp, Lp, Z, dm, m_next, P_next, m_s, P_s});
   }
+}
+
+template <int D, typename Last, typename Step>
+EKS_HD void dense_backward_chunk(int t0, int len, int i_end, const Mat<double, D>& F, const Mat<double, D>& sQ,
+                                 bool f_identity, const Vec<double, D>& m_in, const Mat<double, D>& P_in,
+                                 const Vec<double, D>& m, const Mat<double, D>& P, const Vec<double, D>& eta_s,
+                                 const Mat<double, D>& J_s, const double* __restrict__ filt, size_t fs, Last&& last,
+                                 Step&& step) {
+  dense_backward_walk<D>(
+      t0, len, i_end, F, [&](int) -> const Mat<double, D>& { return sQ; }, f_identity, m_in, P_in, m, P, eta_s, J_s,
+      filt, fs, static_cast<Last&&>(last), static_cast<Step&&>(step));
 }
 
 // K3: exact replay of frames [t0, t0+len).  (m, P): the filtered belief of frame t0-1 (the prior

@@ -104,12 +104,9 @@ size_t diag_em_workspace_bytes(int T, int N) {
   return 9 * plane(nc, N) + 9 * plane(ng, N) + plane64(nc, N);
 }
 
-// E1 + S1 on the caller's workspace: the planes of W (W.pm, W.pP: predicted belief entering every chunk; W.sEta, W.sJ:
-// information after it), the lane mapping and the float64 plane of chunk partials behind them.  Also the first two
-// passes of eks_innovations (eks_innov.hip).
-int diag_em_forward(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, void* ws, EmPlan& E,
-                    hipStream_t st) {
-  const int T = d.n_frames, N = d.n_keypoints * d.state_dim;
+// The planes of W on the caller's workspace (W.pm, W.pP: predicted belief entering every chunk; W.sEta, W.sJ:
+// information after it), the lane mapping, the grid and the float64 plane of chunk partials behind them.
+void diag_em_plan(int T, int N, void* ws, EmPlan& E) {
   SampleWs& W = E.W;
   W = SampleWs{};
   em_geometry(T, W.nc, W.gs, W.ng);
@@ -134,24 +131,34 @@ int diag_em_forward(const eks_dims_t& d, const float* y, const float* var, const
   const int cpw = 64 >> L.nt_log2;                               // chunks per wave
   const long waves = (long)L.ntile * ((W.nc + cpw - 1) / cpw);
   E.grid = dim3((unsigned)((waves + 3) / 4));
-  const dim3 grid = E.grid, block(256);
-  const SampleCall cs{y, var, nullptr, nullptr, nullptr, T, 0u, 0u, 0u, 0u};
-  const bool unit = (d.flags & EKS_FLAG_UNIT_AC) != 0;
-  constexpr int B = kEmChunk;
-  const unsigned gN = (unsigned)(((size_t)W.ng * N + 255) / 256);
+}
 
+// S1: the three scan launches over the chunk elements in W.  Also the scan of eks_smooth_tv (eks_smooth_tv.hip),
+// whose elements carry a per-frame process noise the scan never sees.
+int diag_em_scan(const EmPlan& E, const DiagModel& M, hipStream_t st) {
+  const SampleWs& W = E.W;
+  const unsigned gN = (unsigned)(((size_t)W.ng * W.N + 255) / 256);
+  ProfScope ps("em_scan", st);
+  hipLaunchKernelGGL(em_scan_reduce_kernel, dim3(gN), dim3(256), 0, st, W);
+  hipLaunchKernelGGL(em_scan_kernel, dim3((W.N + 63) / 64), dim3(64), 0, st, W, M);
+  hipLaunchKernelGGL(em_scan_apply_kernel, dim3(gN), dim3(256), 0, st, W);
+  return hip_status(hipGetLastError());
+}
+
+// E1 + S1 on the caller's workspace.  Also the first two passes of eks_innovations (eks_innov.hip).
+int diag_em_forward(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, void* ws, EmPlan& E,
+                    hipStream_t st) {
+  const int T = d.n_frames, N = d.n_keypoints * d.state_dim;
+  diag_em_plan(T, N, ws, E);
+  const SampleCall cs{y, var, nullptr, nullptr, nullptr, T, 0u, 0u, 0u, 0u};
+  constexpr int B = kEmChunk;
   {
     ProfScope ps("em_summarize", st);
-    if (unit) hipLaunchKernelGGL((em_summarize_kernel<B, true>), grid, block, 0, st, L, W, M, cs);
-    else hipLaunchKernelGGL((em_summarize_kernel<B, false>), grid, block, 0, st, L, W, M, cs);
+    if (d.flags & EKS_FLAG_UNIT_AC)
+      hipLaunchKernelGGL((em_summarize_kernel<B, true>), E.grid, dim3(256), 0, st, E.L, E.W, M, cs);
+    else hipLaunchKernelGGL((em_summarize_kernel<B, false>), E.grid, dim3(256), 0, st, E.L, E.W, M, cs);
   }
-  {
-    ProfScope ps("em_scan", st);
-    hipLaunchKernelGGL(em_scan_reduce_kernel, dim3(gN), dim3(256), 0, st, W);
-    hipLaunchKernelGGL(em_scan_kernel, dim3((N + 63) / 64), dim3(64), 0, st, W, M);
-    hipLaunchKernelGGL(em_scan_apply_kernel, dim3(gN), dim3(256), 0, st, W);
-  }
-  return hip_status(hipGetLastError());
+  return diag_em_scan(E, M, st);
 }
 
 int diag_em_stats(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double* Sw, void* ws,

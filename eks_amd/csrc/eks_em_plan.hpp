@@ -1,6 +1,7 @@
-// Lane mapping and launch plan shared by the scalar-chain kernels of eks_em_stats (eks_em.hip) and eks_innovations
-// (eks_innov.hip): both run em_summarize and the grouped Kalman scan (diag_em_forward), then a replay of their own
-// over the same (chain, chunk) lanes.
+// Lane mapping and launch plan shared by the scalar-chain kernels of eks_em_stats (eks_em.hip), eks_innovations
+// (eks_innov.hip) and eks_smooth_tv (eks_smooth_tv.hip): the first two run em_summarize and the grouped Kalman scan
+// (diag_em_forward), the third a summarize of its own and the same scan (diag_em_plan, diag_em_scan); each then
+// replays over the same (chain, chunk) lanes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +35,8 @@ struct EmPlan {
   double* part;   // [nc][N] float64 chunk partials behind the planes
 };
 
+void diag_em_plan(int T, int N, void* ws, EmPlan& E);                       // planes, lane mapping, grid
+int diag_em_scan(const EmPlan& E, const DiagModel& M, hipStream_t st);      // the three scan launches over E.W
 int diag_em_forward(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, void* ws, EmPlan& E,
                     hipStream_t st);
 

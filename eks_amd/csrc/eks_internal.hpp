@@ -147,6 +147,14 @@ size_t dense_innovations_workspace_bytes(int T, int K, int D, int O);
 int dense_innovations(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, float* innov,
                       float* innov_var, float* nis, float* frame_ll, double* loglik, void* ws, size_t ws_bytes,
                       hipStream_t st);
+// eks_smooth with a per-frame process-noise scale (eks_smooth_tv.hip: scalar chains, on eks_em.hip's plan, scan and
+// workspace; eks_dense.hip: general models, always the generic kernels)
+int diag_smooth_tv_check(const eks_dims_t& d);
+int diag_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
+                   const DiagModel& M, float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);
+size_t dense_smooth_tv_workspace_bytes(int T, int K, int D, int O);
+int dense_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
+                    const DenseModel& M, float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M,
                  float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);

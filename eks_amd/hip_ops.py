@@ -200,6 +200,28 @@ def smooth(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False, ou
     return PreparedSmooth(y, var, m0, S0, A, C, Q, s, flags, vs_diag, out)()
 
 
+def smooth_tv(y, var, qscale, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False):
+    """eks_smooth_tv: eks_smooth with one process-noise scale per frame, x_t = A x_{t-1} + N(0, s w_t Q).  qscale is a
+    float32 device tensor (T,) shared by all keypoints or (T, K) frame-major; qscale[t] scales the step INTO frame t and
+    entry 0 is never read.  The precondition 0 <= w <= 1e6, finite, is the caller's (eks_amd.irregular enforces it).
+    Returns (ms, Vs) as smooth()."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
+    s = _chk(s, torch.float64, 's', (K,))
+    if qscale.dim() not in (1, 2):
+        raise ValueError(f'qscale must have shape {(T,)} or {(T, K)}, got {tuple(qscale.shape)}')
+    qscale = _chk(qscale, torch.float32, 'qscale', (T,) if qscale.dim() == 1 else (T, K))
+    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
+    dims = _dims(K, T, D, O, flags)
+    ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device)
+    Vs = torch.empty((T, K, D) if vs_diag else (T, K, D, D), dtype=torch.float32, device=y.device)
+    ws = _workspace(lib.eks_smooth_tv_workspace_bytes(ctypes.byref(dims)), y.device)
+    rc = lib.eks_smooth_tv(ctypes.byref(dims), _ptr(bufs[0]), _ptr(bufs[1]), _ptr(qscale), int(qscale.dim() == 2),
+                           *[_ptr(b) for b in bufs[2:]], _ptr(s), _ptr(ms), _ptr(Vs), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, 'eks_smooth_tv')
+    return ms, Vs
+
+
 def smooth_increments(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False,
                       want=('lag1', 'dmean', 'dV'), want_smooth: bool = True):
     """eks_smooth_increments: eks_smooth plus lag1 = Cov(x_t, x_{t+1} | y), dmean = E[x_{t+1} - x_t | y] and

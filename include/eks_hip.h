@@ -77,6 +77,33 @@ int eks_smooth(const eks_dims_t* dims, const float* y, const float* var, const d
                const double* s, float* ms, float* Vs, void* workspace, size_t workspace_bytes,
                eks_stream_t stream);
 
+/* ---- eks_smooth with one process-noise scale per frame, for sessions with uneven frame intervals (dropped frames,
+ * concatenated sessions, moments of known larger motion).  No reference counterpart.  The model is
+ *     x_0 ~ N(m0, S0),      x_t = A x_{t-1} + N(0, s w_t Q)      for t = 1 .. T-1.
+ * dims, flags (EKS_FLAG_DIAG_MODEL, EKS_FLAG_UNIT_AC, EKS_FLAG_VS_DIAG), y, var, the parameters and the layouts of ms and
+ * Vs are exactly those of eks_smooth.
+ *   qscale               float32 device array; qscale[t] = w_t scales the noise of the step INTO frame t.
+ *                        qscale_per_keypoint == 0: [T], shared by all keypoints; otherwise [T][K], frame-major like y:
+ *                        all D chains of keypoint k read entry [t][k].  ENTRY 0 (row 0) IS NEVER READ.  There is no w_T:
+ *                        where a lane predicts past frame T-1 it uses 1, and no output depends on that value.
+ *   precondition         every w that is read is finite and 0 <= w <= 1e6.  The library does not check it (the Python
+ *                        layer does): a value outside it gives wrong numbers for the keypoints that read it, never a
+ *                        fault.  w = 0 (no motion over the step) and a singular Q are fine.
+ *   scalar chains        float32 lanes, five launches: a summarize and a replay of their own around eks_em_stats'
+ *                        three-launch scan; workspace as eks_em_stats.  Never the windowed replay of eks_smooth (its
+ *                        forgetting bound assumes a constant process noise): the EKS_SMOOTH_WINDOW* knobs have no effect.
+ *                        With w = 1 everywhere the result is eks_smooth's up to the rounding of a differently associated
+ *                        scan.  Full Vs rows need D <= 8, as eks_smooth.
+ *   general models       D <= 6 and O <= 64 (else EKS_ERR_UNSUPPORTED and a workspace size of 0); always the generic
+ *                        float64 summarize / scan / replay kernels of eks_smooth.
+ * Refusals are eks_smooth's plus EKS_ERR_NULL for a NULL qscale and EKS_ERR_SHAPE where a launch index would leave 32
+ * bits (as eks_em_stats); all are returned before anything is enqueued and leave ms and Vs untouched. ------------------ */
+size_t eks_smooth_tv_workspace_bytes(const eks_dims_t* dims);
+int eks_smooth_tv(const eks_dims_t* dims, const float* y, const float* var, const float* qscale,
+                  int32_t qscale_per_keypoint, const double* m0, const double* S0, const double* A, const double* C,
+                  const double* Q, const double* s, float* ms, float* Vs, void* workspace, size_t workspace_bytes,
+                  eks_stream_t stream);
+
 /* ---- joint posterior trajectories: n_draws draws of x_1..x_T from the smoothing distribution p(x | y) of the model
  * eks_smooth smooths (same dims, flags, y, var and parameters; EKS_FLAG_VS_DIAG is ignored).  No reference counterpart:
  * the reference returns the per-frame marginals ms, Vs only (eks/core.py:296-297), which say nothing about how the
