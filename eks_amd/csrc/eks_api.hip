@@ -101,7 +101,7 @@ static int increments_check(const eks_dims_t* d) {
   if (rc != EKS_OK) return rc;
   if (d->flags & EKS_FLAG_DIAG_MODEL) {
     if (!(d->flags & EKS_FLAG_VS_DIAG)) return EKS_ERR_UNSUPPORTED;   // off-diagonals are identically zero
-    return diag_increments_covers(d->n_frames, d->n_keypoints * d->state_dim) ? EKS_OK : EKS_ERR_SHAPE;
+    return diag_chain_covers(d->n_frames, d->n_keypoints * d->state_dim) ? EKS_OK : EKS_ERR_SHAPE;
   }
   if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
   return EKS_OK;
@@ -138,7 +138,7 @@ static int em_check(const eks_dims_t* d) {
   if (rc != EKS_OK) return rc;
   if (d->flags & EKS_FLAG_DIAG_MODEL) {
     if (!(d->flags & EKS_FLAG_VS_DIAG)) return EKS_ERR_UNSUPPORTED;   // a diagonal Q's M-step reads the diagonal only
-    return diag_em_covers(d->n_frames, d->n_keypoints * d->state_dim) ? EKS_OK : EKS_ERR_SHAPE;
+    return diag_chain_covers(d->n_frames, d->n_keypoints * d->state_dim) ? EKS_OK : EKS_ERR_SHAPE;
   }
   if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
   // (dense_em_stats' own launch-index check, here so that the workspace query and the call agree)
@@ -174,7 +174,7 @@ static int innovations_check(const eks_dims_t* d) {
   const int rc = check_dims(d);
   if (rc != EKS_OK) return rc;
   if (d->flags & EKS_FLAG_DIAG_MODEL)
-    return diag_em_covers(d->n_frames, d->n_keypoints * d->state_dim) ? EKS_OK : EKS_ERR_SHAPE;
+    return diag_chain_covers(d->n_frames, d->n_keypoints * d->state_dim) ? EKS_OK : EKS_ERR_SHAPE;
   if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
   return dense_innovations_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim) ? EKS_OK
                                                                                                     : EKS_ERR_SHAPE;

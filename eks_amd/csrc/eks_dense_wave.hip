@@ -646,12 +646,33 @@ bool dense_wave_covers(int T, int K, int D, int O) {
   return dw_units(T, K, dw_chunk_frames(T, K, O)) <= 1024;                       // depth-bound problems: every block resident at once
 }
 
-size_t dense_wave_workspace_bytes(int T, int K, int D) {
-  const size_t cb = (size_t)dw_chunk_frames(T, K, 0);   // (an upper bound for O > 8, which keeps 8 frames)
+// The workspace of a call with cb frames per lane: exclusive prefix / suffix elements per chunk, the aggregate of every
+// 64 chunks, the first record per keypoint, the partial sums (up to 1 + 2 D planes: MODE 2).  Returns the bytes; base ==
+// nullptr: the size alone.
+struct DwWs {
+  double *pre_ex, *suf_ex, *agg, *first, *part;
+};
+static size_t dw_layout(int T, int K, int D, int cb, char* base, DwWs* W) {
   const size_t nc = ((size_t)T + cb - 1) / cb, nwb = (nc + 63) / 64;
   const size_t nv = 3 * D * D + 2 * D + 1, rec = D + D * D;
-  return 2 * align_up(nc * K * nv * 8, 256) + align_up(nwb * K * nv * 8, 256) + align_up((size_t)K * rec * 8, 256) +
-         align_up(nwb * K * (1 + 2 * (size_t)D) * 8, 256);   // partial sums: up to 1 + 2 D planes (MODE 2)
+  size_t at = 0;
+  auto take = [&](size_t doubles) {
+    double* p = base ? reinterpret_cast<double*>(base + at) : nullptr;
+    at += align_up(doubles * 8, 256);
+    return p;
+  };
+  W->pre_ex = take(nc * K * nv);
+  W->suf_ex = take(nc * K * nv);
+  W->agg = take(nwb * K * nv);
+  W->first = take((size_t)K * rec);
+  W->part = take(nwb * K * (1 + 2 * (size_t)D));
+  return at;
+}
+
+// sized for dw_chunk_frames(T, K, 0) frames per lane: an upper bound for O > 8, which keeps 8 frames
+size_t dense_wave_workspace_bytes(int T, int K, int D) {
+  DwWs W;
+  return dw_layout(T, K, D, dw_chunk_frames(T, K, 0), nullptr, &W);
 }
 
 // MODE 2: nll[k] = -loglik (no non-finite substitution in the pupil loss, eks/ibl_pupil_smoother.py:551-552),
@@ -742,19 +763,9 @@ static int dense_wave_run(const eks_dims_t& d, int mode, const float* y, const f
   const int cb = dw_chunk_frames(T, K, O);            // frames per lane: 2 / 4 for short sessions, else 8
   DwGeom G{K, T, (T + cb - 1) / cb, 0};
   G.nwb = (G.nc + 63) / 64;
-  const size_t nv = 3 * D * D + 2 * D + 1, rec = D + D * D;
-  const size_t need = dense_wave_workspace_bytes(T, K, D);
-  if (ws_bytes < need) return EKS_ERR_WORKSPACE;
-  char* p = static_cast<char*>(ws);
-  double* pre_ex = reinterpret_cast<double*>(p);
-  p += align_up((size_t)G.nc * K * nv * 8, 256);
-  double* suf_ex = reinterpret_cast<double*>(p);
-  p += align_up((size_t)G.nc * K * nv * 8, 256);
-  double* agg = reinterpret_cast<double*>(p);
-  p += align_up((size_t)G.nwb * K * nv * 8, 256);
-  double* first = reinterpret_cast<double*>(p);
-  p += align_up((size_t)K * rec * 8, 256);
-  double* part = reinterpret_cast<double*>(p);
+  if (ws_bytes < dense_wave_workspace_bytes(T, K, D)) return EKS_ERR_WORKSPACE;
+  DwWs W;
+  dw_layout(T, K, D, cb, static_cast<char*>(ws), &W);   // this call's own chunk count: never more than the query's
   const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
   const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
   const int units = K * G.nwb;
@@ -765,11 +776,11 @@ static int dense_wave_run(const eks_dims_t& d, int mode, const float* y, const f
     {                                                                                                    \
       ProfScope ps(MD ? "dense_score_summarize" : "dense_summarize", st);                                \
       hipLaunchKernelGGL((dw_summarize_kernel<DD, OO, SS, MD, BB>), grid, block, 0, st, G, M, Mm.s, y,    \
-                         var, rconst, ar.a, ar.q, pre_ex, suf_ex, agg, first);                           \
+                         var, rconst, ar.a, ar.q, W.pre_ex, W.suf_ex, W.agg, W.first);                   \
     }                                                                                                    \
     ProfScope ps(MD ? "dense_score_replay" : "dense_replay", st);                                        \
     hipLaunchKernelGGL((dw_replay_kernel<DD, OO, SS, MD, BB>), grid, block, 0, st, G, M, Mm.s, y, var,    \
-                       rconst, ar.a, ar.q, part, pre_ex, suf_ex, agg, first, ms, Vs, vs_diag);           \
+                       rconst, ar.a, ar.q, W.part, W.pre_ex, W.suf_ex, W.agg, W.first, ms, Vs, vs_diag); \
   }
   // short chunks exist for one wave pair per workgroup only (they are chosen while the units are few) and up to
   // four cameras
@@ -811,9 +822,9 @@ static int dense_wave_run(const eks_dims_t& d, int mode, const float* y, const f
     else
       EKS_DW_S(3, 8, 1, 2)
     if (ar.step && K <= 64 && ar.n_tan == 2)
-      hipLaunchKernelGGL(dw_ar1_finish_step_kernel<3>, dim3(1), dim3(512), 0, st, K, G.nwb, part, nll, dnll, *ar.step);
+      hipLaunchKernelGGL(dw_ar1_finish_step_kernel<3>, dim3(1), dim3(512), 0, st, K, G.nwb, W.part, nll, dnll, *ar.step);
     else
-      hipLaunchKernelGGL(dw_ar1_finish_kernel<3>, dim3(K), dim3(64), 0, st, K, G.nwb, ar.n_tan, part, ar.da, ar.dq, nll,
+      hipLaunchKernelGGL(dw_ar1_finish_kernel<3>, dim3(K), dim3(64), 0, st, K, G.nwb, ar.n_tan, W.part, ar.da, ar.dq, nll,
                          dnll);
     return hip_status(hipGetLastError());
   }
@@ -833,7 +844,7 @@ static int dense_wave_run(const eks_dims_t& d, int mode, const float* y, const f
 #undef EKS_DW
 #undef EKS_DW_S
 #undef EKS_DW_SB
-  if (mode == 1) return dense_score_finish(K, G.nwb, part, part + (size_t)K * G.nwb, nll, dnll, st);
+  if (mode == 1) return dense_score_finish(K, G.nwb, W.part, W.part + (size_t)K * G.nwb, nll, dnll, st);
   return hip_status(hipGetLastError());
 }
 

@@ -1,9 +1,8 @@
 // gfx950 kernels of eks_em_stats on scalar chains (EKS_FLAG_DIAG_MODEL) and of eks_em_scale_step: the E-step
 // statistic Sw = sum_t E[w_t w_t^T | y] of the model eks_smooth runs (formulas in eks_em_lane.hpp) and the closed-form
 // M-step for the process-noise scale.  No reference counterpart.
-//   E1 em_summarize  : lane = (chain, chunk of B frames): the chunk's filter element (reads y, var)
-//   S1 kalman scan x3: belief entering / information after every chunk (grouped, lanes along chains; the sampler's
-//                      kalman_group_* bodies and SampleWs planes, eks_sample_lane.hpp)
+//   E1 summarize     : lane = (chain, chunk of B frames): the chunk's filter element (reads y, var)    } eks_chain.hip,
+//   S1 kalman scan x3: belief entering / information after every chunk (grouped, lanes along chains) } chain_forward
 //   E2 em_replay     : lane = (chain, chunk): filter in registers, fuse, RTS backwards; one float64 partial per lane
 //                      goes to a [chunk][chain] plane (reads y, var; writes nothing of length T)
 //   E3 em_reduce     : per chain, the chunk partials summed in a fixed order that depends on the number of chunks
@@ -12,41 +11,17 @@
 // y and var are read twice.  General models: eks_dense.hip, dense_em.
 #include <hip/hip_runtime.h>
 
+#include "eks_chain_plan.hpp"
 #include "eks_em_lane.hpp"
-#include "eks_em_plan.hpp"
 #include "eks_internal.hpp"
 
 namespace eks {
 
 template <int B, bool UNIT>
-__global__ __launch_bounds__(256) void em_summarize_kernel(EmMap L, SampleWs W, DiagModel M, SampleCall c) {
+__global__ __launch_bounds__(256) void em_replay_kernel(ChainMap L, SampleWs W, DiagModel M, EmCall c) {
   int n, j;
-  if (!em_coords(L, W.N, W.nc, n, j)) return;
-  sample_summarize_lane<B, UNIT>(W, M, c, n, j);
-}
-
-template <int B, bool UNIT>
-__global__ __launch_bounds__(256) void em_replay_kernel(EmMap L, SampleWs W, DiagModel M, EmCall c) {
-  int n, j;
-  if (!em_coords(L, W.N, W.nc, n, j)) return;
+  if (!chain_coords(L, W.N, W.nc, n, j)) return;
   em_replay_lane<B, UNIT>(W, M, c, n, j);
-}
-
-// scan: one thread per (group, chain) or per chain, chains fastest
-__global__ __launch_bounds__(256) void em_scan_reduce_kernel(SampleWs W) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx < W.ng * W.N) kalman_group_reduce(W, idx % W.N, idx / W.N);
-}
-__global__ __launch_bounds__(64) void em_scan_kernel(SampleWs W, DiagModel M) {
-  const int n = blockIdx.x * 64 + threadIdx.x;
-  if (n >= W.N) return;
-  float m, P;
-  load_chain_prior(M, n, m, P);
-  kalman_group_scan(W, n, m, P);
-}
-__global__ __launch_bounds__(256) void em_scan_apply_kernel(SampleWs W) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx < W.ng * W.N) kalman_group_apply(W, idx % W.N, idx / W.N);
 }
 
 // E3: a workgroup takes kEmCols consecutive columns (chains, or matrix entries of the general form); kEmSegs threads
@@ -81,100 +56,24 @@ int em_reduce(const double* part, int nc, int ne, double* Sw, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-static inline size_t plane(size_t rows, int N) { return align_up(rows * (size_t)N * sizeof(float), 256); }
-static inline size_t plane64(size_t rows, int N) { return align_up(rows * (size_t)N * sizeof(double), 256); }
-
-static void em_geometry(int T, int& nc, int& gs, int& ng) {
-  nc = (T + kEmChunk - 1) / kEmChunk;
-  gs = 1;
-  while (gs * gs < nc) ++gs;
-  ng = (nc + gs - 1) / gs;
-}
-
-// every launch indexes its threads with an int
-bool diag_em_covers(int T, int N) {
-  int nc, gs, ng;
-  em_geometry(T, nc, gs, ng);
-  return (size_t)nc * N < (1u << 30);
-}
-
-size_t diag_em_workspace_bytes(int T, int N) {
-  int nc, gs, ng;
-  em_geometry(T, nc, gs, ng);
-  return 9 * plane(nc, N) + 9 * plane(ng, N) + plane64(nc, N);
-}
-
-// The planes of W on the caller's workspace (W.pm, W.pP: predicted belief entering every chunk; W.sEta, W.sJ:
-// information after it), the lane mapping, the grid and the float64 plane of chunk partials behind them.
-void diag_em_plan(int T, int N, void* ws, EmPlan& E) {
-  SampleWs& W = E.W;
-  W = SampleWs{};
-  em_geometry(T, W.nc, W.gs, W.ng);
-  W.N = N;
-  W.n_draws = 0;
-  char* at = static_cast<char*>(ws);
-  auto take = [&](size_t rows) {
-    float* p = reinterpret_cast<float*>(at);
-    at += plane(rows, N);
-    return p;
-  };
-  W.eA = take(W.nc); W.eb = take(W.nc); W.eC = take(W.nc); W.eEta = take(W.nc); W.eJ = take(W.nc);
-  W.pm = take(W.nc); W.pP = take(W.nc); W.sEta = take(W.nc); W.sJ = take(W.nc);
-  W.gA = take(W.ng); W.gb = take(W.ng); W.gC = take(W.ng); W.gEta = take(W.ng); W.gJ = take(W.ng);
-  W.gm = take(W.ng); W.gP = take(W.ng); W.gsEta = take(W.ng); W.gsJ = take(W.ng);
-  E.part = reinterpret_cast<double*>(at);
-
-  EmMap& L = E.L;
-  L.nt_log2 = 0;
-  while ((1 << L.nt_log2) < N && L.nt_log2 < 6) ++L.nt_log2;
-  L.ntile = (N + (1 << L.nt_log2) - 1) >> L.nt_log2;
-  const int cpw = 64 >> L.nt_log2;                               // chunks per wave
-  const long waves = (long)L.ntile * ((W.nc + cpw - 1) / cpw);
-  E.grid = dim3((unsigned)((waves + 3) / 4));
-}
-
-// S1: the three scan launches over the chunk elements in W.  Also the scan of eks_smooth_tv (eks_smooth_tv.hip),
-// whose elements carry a per-frame process noise the scan never sees.
-int diag_em_scan(const EmPlan& E, const DiagModel& M, hipStream_t st) {
-  const SampleWs& W = E.W;
-  const unsigned gN = (unsigned)(((size_t)W.ng * W.N + 255) / 256);
-  ProfScope ps("em_scan", st);
-  hipLaunchKernelGGL(em_scan_reduce_kernel, dim3(gN), dim3(256), 0, st, W);
-  hipLaunchKernelGGL(em_scan_kernel, dim3((W.N + 63) / 64), dim3(64), 0, st, W, M);
-  hipLaunchKernelGGL(em_scan_apply_kernel, dim3(gN), dim3(256), 0, st, W);
-  return hip_status(hipGetLastError());
-}
-
-// E1 + S1 on the caller's workspace.  Also the first two passes of eks_innovations (eks_innov.hip).
-int diag_em_forward(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, void* ws, EmPlan& E,
-                    hipStream_t st) {
-  const int T = d.n_frames, N = d.n_keypoints * d.state_dim;
-  diag_em_plan(T, N, ws, E);
-  const SampleCall cs{y, var, nullptr, nullptr, nullptr, T, 0u, 0u, 0u, 0u};
-  constexpr int B = kEmChunk;
-  {
-    ProfScope ps("em_summarize", st);
-    if (d.flags & EKS_FLAG_UNIT_AC)
-      hipLaunchKernelGGL((em_summarize_kernel<B, true>), E.grid, dim3(256), 0, st, E.L, E.W, M, cs);
-    else hipLaunchKernelGGL((em_summarize_kernel<B, false>), E.grid, dim3(256), 0, st, E.L, E.W, M, cs);
-  }
-  return diag_em_scan(E, M, st);
-}
+// the planes of the forward pass and the float64 plane of chunk partials behind them; nothing of length T
+size_t diag_em_workspace_bytes(int T, int N) { return chain_workspace_bytes(T, N, 0, true); }
 
 int diag_em_stats(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double* Sw, void* ws,
                   size_t ws_bytes, hipStream_t st) {
   const int T = d.n_frames, N = d.n_keypoints * d.state_dim;
-  if (!diag_em_covers(T, N)) return EKS_ERR_SHAPE;
+  if (!diag_chain_covers(T, N)) return EKS_ERR_SHAPE;
   if (ws_bytes < diag_em_workspace_bytes(T, N)) return EKS_ERR_WORKSPACE;
-  EmPlan E;
-  const int rc = diag_em_forward(d, y, var, M, ws, E, st);
+  const ChainPlan E = chain_plan(T, N, 0, true, ws);
+  const bool unit = (d.flags & EKS_FLAG_UNIT_AC) != 0;
+  const SampleCall cs{y, var, nullptr, nullptr, nullptr, T, 0u, 0u, 0u, 0u};
+  const int rc = chain_forward(E, M, cs, unit, "em_summarize", "em_scan", st);
   if (rc != EKS_OK) return rc;
   const EmCall c{y, var, E.part, T};
   {
     ProfScope ps("em_replay", st);
-    if (d.flags & EKS_FLAG_UNIT_AC)
-      hipLaunchKernelGGL((em_replay_kernel<kEmChunk, true>), E.grid, dim3(256), 0, st, E.L, E.W, M, c);
-    else hipLaunchKernelGGL((em_replay_kernel<kEmChunk, false>), E.grid, dim3(256), 0, st, E.L, E.W, M, c);
+    if (unit) hipLaunchKernelGGL((em_replay_kernel<kChainChunk, true>), dim3(E.blocks), dim3(256), 0, st, E.L, E.W, M, c);
+    else hipLaunchKernelGGL((em_replay_kernel<kChainChunk, false>), dim3(E.blocks), dim3(256), 0, st, E.L, E.W, M, c);
   }
   return em_reduce(E.part, E.W.nc, N, Sw, st);
 }

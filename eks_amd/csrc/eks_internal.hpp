@@ -98,6 +98,10 @@ int32_t* nll_ws_tickets(void* ws, int T, int N, int n_cand);   // the tile ticke
 int adam_prepare(int n_blocks, int K, const int32_t* offs, const int32_t* members, int32_t* kp_block,
                  int32_t* counter_a, int32_t* counter_b, hipStream_t st);
 
+// The scalar-chain forms of eks_sample, eks_smooth_increments, eks_em_stats, eks_innovations and eks_smooth_tv share
+// geometry, workspace layout, summarize and scan (eks_chain_plan.hpp, eks_chain.hip); this is their launch-index limit.
+bool diag_chain_covers(int T, int N);
+
 // joint posterior sampling (eks_sample.hip: scalar chains; eks_sample_dense.hip: general models)
 size_t diag_sample_workspace_bytes(int T, int N, int n_draws);
 int diag_sample(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, int n_draws, uint64_t seed,
@@ -119,7 +123,6 @@ struct DenseModel {
 };
 // eks_smooth plus lag-one covariances and the posterior of increments (eks_increments.hip: scalar chains;
 // eks_dense.hip: general models, always the generic kernels)
-bool diag_increments_covers(int T, int N);
 size_t diag_increments_workspace_bytes(int T, int N);
 int diag_increments(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, float* ms, float* Vs,
                     float* lag1, float* dmean, float* dV, void* ws, size_t ws_bytes, hipStream_t st);
@@ -128,7 +131,6 @@ int dense_increments(const eks_dims_t& d, const float* y, const float* var, cons
                      float* lag1, float* dmean, float* dV, void* ws, size_t ws_bytes, hipStream_t st);
 // E-step statistic Sw = sum_t E[w_t w_t^T | y] and the M-step for the scale (eks_em.hip: scalar chains, the
 // fixed-order reduce of the chunk partials and the step; eks_dense.hip: general models, always the generic kernels)
-bool diag_em_covers(int T, int N);
 size_t diag_em_workspace_bytes(int T, int N);
 int diag_em_stats(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double* Sw, void* ws,
                   size_t ws_bytes, hipStream_t st);
@@ -139,16 +141,16 @@ int em_reduce(const double* part, int nc, int ne, double* Sw, hipStream_t st);
 int em_scale_step(const eks_dims_t& d, const double* Q, const double* Sw, int n_blocks, const int32_t* offs,
                   const int32_t* members, double lo, double hi, double tol, int max_iters, double* state,
                   double* s_keypoint, int32_t* n_active, hipStream_t st);
-// one-step-ahead prediction errors and the exact log-likelihood (eks_innov.hip: scalar chains, on eks_em.hip's
-// summarize / scan and workspace; eks_dense.hip: general models, always the generic kernels)
+// one-step-ahead prediction errors and the exact log-likelihood (eks_innov.hip: scalar chains, on eks_em_stats'
+// workspace; eks_dense.hip: general models, always the generic kernels)
 int diag_innovations(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, float* innov,
                      float* innov_var, double* loglik, void* ws, size_t ws_bytes, hipStream_t st);
 size_t dense_innovations_workspace_bytes(int T, int K, int D, int O);
 int dense_innovations(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, float* innov,
                       float* innov_var, float* nis, float* frame_ll, double* loglik, void* ws, size_t ws_bytes,
                       hipStream_t st);
-// eks_smooth with a per-frame process-noise scale (eks_smooth_tv.hip: scalar chains, on eks_em.hip's plan, scan and
-// workspace; eks_dense.hip: general models, always the generic kernels)
+// eks_smooth with a per-frame process-noise scale (eks_smooth_tv.hip: scalar chains, on eks_em_stats' workspace;
+// eks_dense.hip: general models, always the generic kernels)
 int diag_smooth_tv_check(const eks_dims_t& d);
 int diag_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
                    const DiagModel& M, float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);

@@ -941,30 +941,37 @@ static void lag_geometry(int T, int N, int* nch_out, int* cl_out) {
   *cl_out = (int)cl;
 }
 
-// [part : nch x 256 x N doubles][ck : N x 256 doubles][yT : N x (T rounded up to 16) floats]
-size_t diag_lag_adam_workspace_bytes(int T, int N) {
-  if (T < kLaMinT) return 0;
-  int nch, cl;
-  lag_geometry(T, N, &nch, &cl);
-  return align_up((size_t)nch * kLaL * N * sizeof(double), 256) + align_up((size_t)N * kLaL * sizeof(double), 256) +
-         align_up((size_t)N * (((size_t)T + 15) / 16 * 16) * sizeof(float), 256);
-}
-
 struct LagWs {
   double *part, *ck;
   float* yT;
   int nch, cl;
 };
+// [part : nch x 256 x N doubles][ck : N x 256 doubles][yT : N x (T rounded up to 16) floats]; returns the bytes
+// (base == nullptr: the size query)
+static size_t lag_layout(int T, int N, char* base, LagWs* W) {
+  lag_geometry(T, N, &W->nch, &W->cl);
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + at : nullptr;
+    at += align_up(bytes, 256);
+    return p;
+  };
+  W->part = reinterpret_cast<double*>(take((size_t)W->nch * kLaL * N * sizeof(double)));
+  W->ck = reinterpret_cast<double*>(take((size_t)N * kLaL * sizeof(double)));
+  W->yT = reinterpret_cast<float*>(take((size_t)N * (((size_t)T + 15) / 16 * 16) * sizeof(float)));
+  return at;
+}
+
+size_t diag_lag_adam_workspace_bytes(int T, int N) {
+  if (T < kLaMinT) return 0;
+  LagWs W;
+  return lag_layout(T, N, nullptr, &W);
+}
+
 static int lag_ws(int T, int N, void* ws, size_t ws_bytes, LagWs* W) {
   if (ws_bytes < diag_lag_adam_workspace_bytes(T, N)) return EKS_ERR_WORKSPACE;
-  lag_geometry(T, N, &W->nch, &W->cl);
+  lag_layout(T, N, static_cast<char*>(ws), W);
   if ((long)(W->cl + kRgHist + 160) * N * 4 >= (1L << 31)) return EKS_ERR_UNSUPPORTED;   // 32-bit row offsets of a chunk
-  char* p = static_cast<char*>(ws);
-  W->part = reinterpret_cast<double*>(p);
-  p += align_up((size_t)W->nch * kLaL * N * sizeof(double), 256);
-  W->ck = reinterpret_cast<double*>(p);
-  p += align_up((size_t)N * kLaL * sizeof(double), 256);
-  W->yT = reinterpret_cast<float*>(p);
   return EKS_OK;
 }
 

@@ -3,64 +3,27 @@
 // sums the chunk partials in em_reduce's order.  It is not a fallback: nothing under eks_amd/ loads it.
 #include <vector>
 
+#include "chain_sim.hpp"
 #include "eks_em_lane.hpp"
 
 using namespace eks;
 
 template <int B, bool UNIT>
 static void run(int T, int N, const DiagModel& M, const float* y, const float* var, int gs, double* Sw) {
-  SampleWs W{};
-  W.N = N;
-  W.nc = (T + B - 1) / B;
-  W.gs = gs;
-  W.ng = (W.nc + gs - 1) / gs;
-  W.n_draws = 0;
-  const size_t pc = (size_t)W.nc * N, pg = (size_t)W.ng * N;
-  std::vector<float> buf(9 * pc + 9 * pg);
-  std::vector<double> part(pc, -1.0);
-  float* at = buf.data();
-  auto take = [&](size_t n) { float* p = at; at += n; return p; };
-  W.eA = take(pc); W.eb = take(pc); W.eC = take(pc); W.eEta = take(pc); W.eJ = take(pc);
-  W.pm = take(pc); W.pP = take(pc); W.sEta = take(pc); W.sJ = take(pc);
-  W.gA = take(pg); W.gb = take(pg); W.gC = take(pg); W.gEta = take(pg); W.gJ = take(pg);
-  W.gm = take(pg); W.gP = take(pg); W.gsEta = take(pg); W.gsJ = take(pg);
+  ChainSimWs S(T, N, B, gs, 0, true);
+  const SampleWs& W = S.W;
   const SampleCall cs{y, var, nullptr, nullptr, nullptr, T, 0u, 0u, 0u, 0u};
-  const EmCall c{y, var, part.data(), T};
-  for (int j = 0; j < W.nc; ++j)
-    for (int n = 0; n < N; ++n) sample_summarize_lane<B, UNIT>(W, M, cs, n, j);
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_reduce(W, n, g);
-  for (int n = 0; n < N; ++n) {
-    float m, P;
-    load_chain_prior(M, n, m, P);
-    kalman_group_scan(W, n, m, P);
-  }
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_apply(W, n, g);
+  const EmCall c{y, var, S.part, T};
+  chain_sim_forward<B, UNIT>(W, M, cs);
   for (int j = 0; j < W.nc; ++j)
     for (int n = 0; n < N; ++n) em_replay_lane<B, UNIT>(W, M, c, n, j);
-  // em_reduce's order: 16 contiguous runs of ceil(nc / 16) chunks, then the run sums in run order
-  const int per = (W.nc + 15) / 16;
-  for (int n = 0; n < N; ++n) {
-    double total = 0.0;
-    for (int r = 0; r < 16; ++r) {
-      double acc = 0.0;
-      for (int j = r * per; j < W.nc && j < (r + 1) * per; ++j) acc += part[(size_t)j * N + n];
-      total += acc;
-    }
-    Sw[n] = total;
-  }
+  chain_sim_reduce(W, S.part, Sw);
 }
 
 // gs: chunks per scan group (<= 0: the library's choice, ceil(sqrt(number of chunks)))
 extern "C" int sim_em(int T, int N, int D, int B, int gs, int unit, const float* y, const float* var, const double* m0,
                       const double* S0, const double* A, const double* C, const double* Q, const double* s, double* Sw) {
   const DiagModel M{m0, S0, A, C, Q, s, D};
-  if (gs <= 0) {
-    const int nc = (T + B - 1) / B;
-    gs = 1;
-    while (gs * gs < nc) ++gs;
-  }
 #define RUN(BB)                                            \
   case BB:                                                 \
     if (unit) run<BB, true>(T, N, M, y, var, gs, Sw);      \

@@ -3,6 +3,7 @@
 // kernels' order of passes.  It is not a fallback: nothing under eks_amd/ loads it.
 #include <vector>
 
+#include "chain_sim.hpp"
 #include "eks_increments_lane.hpp"
 
 using namespace eks;
@@ -11,32 +12,10 @@ using namespace eks;
 // writes ms and Vs only - what the increments replay has to reproduce bit for bit.
 template <int B, bool UNIT>
 static void run(int T, int N, const DiagModel& M, const IncrementsCall& c, int gs, int plain) {
-  SampleWs W{};
-  W.N = N;
-  W.nc = (T + B - 1) / B;
-  W.gs = gs;
-  W.ng = (W.nc + gs - 1) / gs;
-  W.n_draws = 0;
-  const size_t pc = (size_t)W.nc * N, pg = (size_t)W.ng * N;
-  std::vector<float> buf(9 * pc + 9 * pg);
-  float* at = buf.data();
-  auto take = [&](size_t n) { float* p = at; at += n; return p; };
-  W.eA = take(pc); W.eb = take(pc); W.eC = take(pc); W.eEta = take(pc); W.eJ = take(pc);
-  W.pm = take(pc); W.pP = take(pc); W.sEta = take(pc); W.sJ = take(pc);
-  W.gA = take(pg); W.gb = take(pg); W.gC = take(pg); W.gEta = take(pg); W.gJ = take(pg);
-  W.gm = take(pg); W.gP = take(pg); W.gsEta = take(pg); W.gsJ = take(pg);
+  ChainSimWs S(T, N, B, gs, 0, false);
+  const SampleWs& W = S.W;
   const SampleCall cs{c.y, c.var, nullptr, nullptr, nullptr, T, 0u, 0u, 0u, 0u};
-  for (int j = 0; j < W.nc; ++j)
-    for (int n = 0; n < N; ++n) sample_summarize_lane<B, UNIT>(W, M, cs, n, j);
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_reduce(W, n, g);
-  for (int n = 0; n < N; ++n) {
-    float m, P;
-    load_chain_prior(M, n, m, P);
-    kalman_group_scan(W, n, m, P);
-  }
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_apply(W, n, g);
+  chain_sim_forward<B, UNIT>(W, M, cs);
   const bool all = c.ms && c.Vs && c.lag1 && c.dmean && c.dV;
   for (int j = 0; j < W.nc; ++j)
     for (int n = 0; n < N; ++n) {
@@ -59,11 +38,6 @@ extern "C" int sim_increments(int T, int N, int D, int B, int gs, int unit, int 
                               const double* s, float* ms, float* Vs, float* lag1, float* dmean, float* dV) {
   const DiagModel M{m0, S0, A, C, Q, s, D};
   const IncrementsCall c{y, var, ms, Vs, lag1, dmean, dV, T};
-  if (gs <= 0) {
-    const int nc = (T + B - 1) / B;
-    gs = 1;
-    while (gs * gs < nc) ++gs;
-  }
 #define RUN(BB)                                         \
   case BB:                                              \
     if (unit) run<BB, true>(T, N, M, c, gs, plain);     \

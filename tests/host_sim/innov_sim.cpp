@@ -4,6 +4,7 @@
 #include <cstring>
 #include <vector>
 
+#include "chain_sim.hpp"
 #include "eks_innov_lane.hpp"
 
 using namespace eks;
@@ -16,34 +17,11 @@ struct NoStore {
 template <int B, bool UNIT>
 static int run(int T, int N, const DiagModel& M, const float* y, const float* var, int gs, float* innov,
                float* innov_var, double* loglik) {
-  SampleWs W{};
-  W.N = N;
-  W.nc = (T + B - 1) / B;
-  W.gs = gs;
-  W.ng = (W.nc + gs - 1) / gs;
-  W.n_draws = 0;
-  const size_t pc = (size_t)W.nc * N, pg = (size_t)W.ng * N;
-  std::vector<float> buf(9 * pc + 9 * pg);
-  std::vector<double> part(pc, -1.0);
-  float* at = buf.data();
-  auto take = [&](size_t n) { float* p = at; at += n; return p; };
-  W.eA = take(pc); W.eb = take(pc); W.eC = take(pc); W.eEta = take(pc); W.eJ = take(pc);
-  W.pm = take(pc); W.pP = take(pc); W.sEta = take(pc); W.sJ = take(pc);
-  W.gA = take(pg); W.gb = take(pg); W.gC = take(pg); W.gEta = take(pg); W.gJ = take(pg);
-  W.gm = take(pg); W.gP = take(pg); W.gsEta = take(pg); W.gsJ = take(pg);
+  ChainSimWs S(T, N, B, gs, 0, true);
+  const SampleWs& W = S.W;
   const SampleCall cs{y, var, nullptr, nullptr, nullptr, T, 0u, 0u, 0u, 0u};
-  const InnovCall c{y, var, innov, innov_var, loglik ? part.data() : nullptr, T};
-  for (int j = 0; j < W.nc; ++j)
-    for (int n = 0; n < N; ++n) sample_summarize_lane<B, UNIT>(W, M, cs, n, j);
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_reduce(W, n, g);
-  for (int n = 0; n < N; ++n) {
-    float m, P;
-    load_chain_prior(M, n, m, P);
-    kalman_group_scan(W, n, m, P);
-  }
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_apply(W, n, g);
+  const InnovCall c{y, var, innov, innov_var, loglik ? S.part : nullptr, T};
+  chain_sim_forward<B, UNIT>(W, M, cs);
   int mismatches = 0;
   for (int j = 0; j < W.nc; ++j)
     for (int n = 0; n < N; ++n) {
@@ -60,19 +38,7 @@ static int run(int T, int N, const DiagModel& M, const float* y, const float* va
       innov_rows<B, UNIT>(b0, b1, len, p, m2, P2, false, NoStore{});
       mismatches += std::memcmp(&m1, &m2, 4) != 0 || std::memcmp(&P1, &P2, 4) != 0;
     }
-  if (loglik) {
-    // em_reduce's order: 16 contiguous runs of ceil(nc / 16) chunks, then the run sums in run order
-    const int per = (W.nc + 15) / 16;
-    for (int n = 0; n < N; ++n) {
-      double total = 0.0;
-      for (int r = 0; r < 16; ++r) {
-        double acc = 0.0;
-        for (int j = r * per; j < W.nc && j < (r + 1) * per; ++j) acc += part[(size_t)j * N + n];
-        total += acc;
-      }
-      loglik[n] = total;
-    }
-  }
+  if (loglik) chain_sim_reduce(W, S.part, loglik);
   return mismatches;
 }
 
@@ -82,11 +48,6 @@ extern "C" int sim_innov(int T, int N, int D, int B, int gs, int unit, const flo
                          const double* m0, const double* S0, const double* A, const double* C, const double* Q,
                          const double* s, float* innov, float* innov_var, double* loglik) {
   const DiagModel M{m0, S0, A, C, Q, s, D};
-  if (gs <= 0) {
-    const int nc = (T + B - 1) / B;
-    gs = 1;
-    while (gs * gs < nc) ++gs;
-  }
 #define RUN(BB)                                                                          \
   case BB:                                                                               \
     return unit ? run<BB, true>(T, N, M, y, var, gs, innov, innov_var, loglik)           \

@@ -4,42 +4,16 @@
 #include <algorithm>
 #include <vector>
 
-#include "eks_sample_lane.hpp"
+#include "chain_sim.hpp"
 
 using namespace eks;
 
 template <int B, bool UNIT>
 static void run(int T, int N, const DiagModel& M, const SampleCall& c, int n_draws, int gs) {
-  SampleWs W;
-  W.N = N;
-  W.nc = (T + B - 1) / B;
-  W.gs = gs;
-  W.ng = (W.nc + gs - 1) / gs;
-  W.n_draws = n_draws;
-  const size_t pc = (size_t)W.nc * N, pg = (size_t)W.ng * N;
-  std::vector<float> buf(10 * pc + n_draws * pc + 10 * pg + n_draws * pg);
-  float* at = buf.data();
-  auto take = [&](size_t n) { float* p = at; at += n; return p; };
-  W.eA = take(pc); W.eb = take(pc); W.eC = take(pc); W.eEta = take(pc); W.eJ = take(pc);
-  W.pm = take(pc); W.pP = take(pc); W.sEta = take(pc); W.sJ = take(pc);
-  W.gam = take(pc);
-  W.beta = take(n_draws * pc);
-  W.gA = take(pg); W.gb = take(pg); W.gC = take(pg); W.gEta = take(pg); W.gJ = take(pg);
-  W.gm = take(pg); W.gP = take(pg); W.gsEta = take(pg); W.gsJ = take(pg);
-  W.hG = take(pg);
-  W.hB = take(n_draws * pg);
+  ChainSimWs S(T, N, B, gs, n_draws, false);
+  const SampleWs& W = S.W;
   const bool inj = c.noise != nullptr;
-  for (int j = 0; j < W.nc; ++j)
-    for (int n = 0; n < N; ++n) sample_summarize_lane<B, UNIT>(W, M, c, n, j);
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_reduce(W, n, g);
-  for (int n = 0; n < N; ++n) {
-    float m, P;
-    load_chain_prior(M, n, m, P);
-    kalman_group_scan(W, n, m, P);
-  }
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_apply(W, n, g);
+  chain_sim_forward<B, UNIT>(W, M, c);
   for (int j = 0; j < W.nc; ++j)
     for (int n = 0; n < N; ++n) {
       if (inj) sample_beta_lane<B, UNIT, true>(W, M, c, n, j);
@@ -67,11 +41,6 @@ extern "C" int sim_sample(int T, int N, int D, int B, int gs, int unit, const fl
   const DiagModel M{m0, S0, A, C, Q, s, D};
   const SampleCall c{y, var, noise, ms, draws, T, (uint32_t)seed, (uint32_t)(seed >> 32),
                      (uint32_t)first_keypoint * (uint32_t)D, (uint32_t)first_draw};
-  if (gs <= 0) {
-    const int nc = (T + B - 1) / B;
-    gs = 1;
-    while (gs * gs < nc) ++gs;
-  }
 #define RUN(BB)                                        \
   case BB:                                             \
     if (unit) run<BB, true>(T, N, M, c, n_draws, gs);  \
@@ -104,3 +73,48 @@ extern "C" void sim_sample_noise(int T, int N, int n_draws, unsigned long long s
         for (int i = 0; i < 4 && 4 * tq + i < T; ++i) noise[((size_t)d * T + 4 * tq + i) * N + n] = z[i];
       }
 }
+
+// A stand-alone run for sanitizer builds of the lane header (g++ -fsanitize=address,undefined -DSAMPLE_SIM_MAIN): odd
+// sizes through every chunk length, one and three draws, the generator's normals and the same normals injected - which
+// must give the same bits; everything written must be finite.
+#ifdef SAMPLE_SIM_MAIN
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+int main() {
+  int bad = 0;
+  for (int B : {4, 8, 16, 32})
+    for (int T : {1, 2, 31, 33, 129, 1000})
+      for (int unit = 0; unit < 2; ++unit)
+        for (int n_draws : {1, 3}) {
+          const int K = 3, D = 2, N = K * D;
+          std::vector<float> y((size_t)T * N), var((size_t)T * N);
+          for (size_t i = 0; i < y.size(); ++i) {
+            y[i] = (float)((i * 37) % 101) * 0.1f;
+            var[i] = 0.5f + (float)((i * 13) % 7);
+          }
+          std::vector<double> m0(N, 0.0), S0(K * D * D, 0.0), A(K * D * D, 0.0), C(K * D * D, 0.0), Q(K * D * D, 0.0),
+              s(K, 2.0);
+          for (int k = 0; k < K; ++k)
+            for (int d = 0; d < D; ++d) {
+              const size_t dd = (size_t)k * D * D + d * (D + 1);
+              S0[dd] = 3.0; Q[dd] = 1.0;
+              A[dd] = unit ? 1.0 : 0.98;
+              C[dd] = unit ? 1.0 : 1.3;
+            }
+          const size_t TN = (size_t)T * N;
+          std::vector<float> noise(n_draws * TN), ms(TN, NAN), draws(n_draws * TN, NAN), ms2(TN, NAN), draws2(n_draws * TN, NAN);
+          sim_sample_noise(T, N, n_draws, 1234u, 0, 0, noise.data());
+          bad += sim_sample(T, N, D, B, 0, unit, y.data(), var.data(), m0.data(), S0.data(), A.data(), C.data(), Q.data(),
+                            s.data(), n_draws, 1234u, 0, 0, nullptr, ms.data(), draws.data());
+          bad += sim_sample(T, N, D, B, 0, unit, y.data(), var.data(), m0.data(), S0.data(), A.data(), C.data(), Q.data(),
+                            s.data(), n_draws, 1234u, 0, 0, noise.data(), ms2.data(), draws2.data());
+          for (size_t i = 0; i < TN; ++i) bad += !std::isfinite(ms[i]);
+          for (size_t i = 0; i < draws.size(); ++i) bad += !std::isfinite(draws[i]);
+          bad += std::memcmp(ms.data(), ms2.data(), TN * sizeof(float)) != 0;
+          bad += std::memcmp(draws.data(), draws2.data(), draws.size() * sizeof(float)) != 0;
+        }
+  std::printf("sample_sim: %s\n", bad ? "FAILED" : "ok");
+  return bad != 0;
+}
+#endif

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <vector>
 
+#include "chain_sim.hpp"
 #include "eks_smooth_tv_lane.hpp"
 
 using namespace eks;
@@ -21,32 +22,12 @@ static bool same(const float* a, const float* b, int n) { return std::memcmp(a, 
 template <int B, bool UNIT>
 static int run(int T, int N, int K, const DiagModel& M, const float* y, const float* var, const float* qscale,
                int per_keypoint, int gs, int compare, float* ms, float* Vs) {
-  SampleWs W{};
-  W.N = N;
-  W.nc = (T + B - 1) / B;
-  W.gs = gs;
-  W.ng = (W.nc + gs - 1) / gs;
-  W.n_draws = 0;
-  const size_t pc = (size_t)W.nc * N, pg = (size_t)W.ng * N;
-  std::vector<float> buf(9 * pc + 9 * pg);
-  float* at = buf.data();
-  auto take = [&](size_t n) { float* p = at; at += n; return p; };
-  W.eA = take(pc); W.eb = take(pc); W.eC = take(pc); W.eEta = take(pc); W.eJ = take(pc);
-  W.pm = take(pc); W.pP = take(pc); W.sEta = take(pc); W.sJ = take(pc);
-  W.gA = take(pg); W.gb = take(pg); W.gC = take(pg); W.gEta = take(pg); W.gJ = take(pg);
-  W.gm = take(pg); W.gP = take(pg); W.gsEta = take(pg); W.gsJ = take(pg);
+  ChainSimWs S(T, N, B, gs, 0, false);
+  const SampleWs& W = S.W;
   const SmoothTvCall c{y, var, qscale, ms, Vs, T, K, per_keypoint};
   for (int j = 0; j < W.nc; ++j)
     for (int n = 0; n < N; ++n) smooth_tv_summarize_lane<B, UNIT>(W, M, c, n, j);
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_reduce(W, n, g);
-  for (int n = 0; n < N; ++n) {
-    float m, P;
-    load_chain_prior(M, n, m, P);
-    kalman_group_scan(W, n, m, P);
-  }
-  for (int g = 0; g < W.ng; ++g)
-    for (int n = 0; n < N; ++n) kalman_group_apply(W, n, g);
+  chain_sim_scan(W, M);
   int mismatches = 0;
   for (int j = 0; j < W.nc; ++j)
     for (int n = 0; n < N; ++n) {
@@ -92,11 +73,6 @@ extern "C" int sim_smooth_tv(int T, int N, int D, int B, int gs, int unit, const
                              const double* C, const double* Q, const double* s, int compare, float* ms, float* Vs) {
   const DiagModel M{m0, S0, A, C, Q, s, D};
   const int K = N / D;
-  if (gs <= 0) {
-    const int nc = (T + B - 1) / B;
-    gs = 1;
-    while (gs * gs < nc) ++gs;
-  }
 #define RUN(BB)                                                                                           \
   case BB:                                                                                                \
     return unit ? run<BB, true>(T, N, K, M, y, var, qscale, per_keypoint, gs, compare, ms, Vs)            \

@@ -47,7 +47,7 @@ torch = pytest.importorskip('torch')
 
 PARAMS = inc.PARAMS
 _dev = inc._dev
-B = 32                  # frames per lane of the scalar-chain kernels (kChunk, kEmChunk, kIncrementsChunk, kSampleChunk)
+B = 32                  # frames per lane of the scalar-chain kernels (kChunk, kChainChunk)
 B_DENSE = 16            # dense_chunk() of a small general model
 T_LANES = (B + 1, 64 * B + 1)                 # one frame past a chunk, one frame past 64 chunks
 CHAINS = ((1, 1), (65, 1), (3 * 64 + 1, 1))   # N = 1 (packed lanes), one chain past a tile, one past three tiles

@@ -141,7 +141,7 @@ def test_same_noise_parity_with_the_float64_reference_at_size(T, K, unit, sval):
     assert (np.abs(ms - ms_s) / np.abs(ms_s).max(axis=0)).max() < 1e-5
 
 
-# N = K D chains against the lane mapping of sample_coords (eks_sample.hip): 2^nt_log2 = min(64, pow2ceil(N)) chains
+# N = K D chains against the lane mapping of chain_coords (eks_chain_plan.hpp): 2^nt_log2 = min(64, pow2ceil(N)) chains
 # per wave row, so N = 1, 3, 6 put 64, 16, 8 chunks of one chain side by side in a wave (with idle lanes at N = 3, 6);
 # N = 63 leaves one lane of every row idle; N = 65, 130, 195 have a ragged last tile of 1, 2, 3 chains.
 EDGE_CHAINS = [(1, 1), (3, 1), (1, 3), (3, 2), (21, 3), (63, 1), (65, 1), (65, 2), (65, 3)]

@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip('torch')
 
-B = 32                                        # kEmChunk: frames per lane of the scalar-chain kernels
+B = 32                                        # kChainChunk: frames per lane of the scalar-chain kernels
 T_EDGES = (1, 2, 3, B - 1, B, B + 1, 64 * B - 1, 64 * B + 1, 2 * 64 * B + 5)   # .., the 64-chunk edge, three blocks of 64
 
 
