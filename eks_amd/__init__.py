@@ -26,6 +26,7 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'innovations_singlecam': 'diagnostics',
         'process_noise_scale_from_times': 'irregular', 'smooth_time_varying': 'irregular',
         'smooth_singlecam_irregular': 'irregular',
+        'smooth_robust': 'robust', 'smooth_singlecam_robust': 'robust',
     }
     if name in table:
         return getattr(importlib.import_module(f'.{table[name]}', __name__), name)

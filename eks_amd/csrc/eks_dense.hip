@@ -20,6 +20,7 @@
 #include "eks_increments_lane.hpp"
 #include "eks_innov_lane.hpp"
 #include "eks_internal.hpp"
+#include "eks_smooth_robust_lane.hpp"
 #include "eks_smooth_tv_lane.hpp"
 
 namespace eks {
@@ -557,6 +558,74 @@ int dense_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const
     ProfScope ps("dense_tv_replay", st);
     hipLaunchKernelGGL(dense_tv_replay_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs, qscale, pk,
                        L.pre, L.suf, L.bprior, L.bsuffix, L.filt, ms, Vs, vs_diag);
+  })
+  return hip_status(hipGetLastError());
+}
+
+// ---- eks_smooth_robust on general models: n_iters passes of the generic organisation under r / lam -------------------
+// dense_summarize -> dense_scan -> dense_scan_blocks as they are on an observation source that divides r by
+// lam[t][k][o] (eks_smooth_robust_lane.hpp: RobustObs), then a replay of its own that updates the weights in place
+// (middle passes) or writes ms, Vs (the last).  Correct, not tuned: always the generic kernels and their layout, with
+// one [T][K][O] float plane of weights behind it.
+template <int D>
+__global__ __launch_bounds__(64) void dense_robust_replay_kernel(DenseGeom G, DenseModelPtrs M,
+                                                                const double* __restrict__ s, RobustObs<D> obs,
+                                                                float* lam, double nu, int last, float* change,
+                                                                const double* __restrict__ pre,
+                                                                const double* __restrict__ suf,
+                                                                const double* __restrict__ bprior,
+                                                                const double* __restrict__ bsuffix,
+                                                                double* __restrict__ filt, float* __restrict__ ms,
+                                                                float* __restrict__ Vs, int vs_diag) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.nc) return;
+  constexpr int REC = D + D * D;
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  Vec<double, D> m, eta;
+  Mat<double, D> P, J;
+  dense_chunk_boundary<D>(G, M, k, j, j, pre, suf, bprior, bsuffix, m, P, eta, J);   // one element per lane (Bs == B)
+  const int t0 = j * G.B, len = min(G.B, G.T - t0);
+  const double ch = dense_robust_replay_chunk<D>(obs, lam, nu, last != 0, k, t0, len, F, sQ, fid, m, P, eta, J,
+                                                 filt + (size_t)t0 * REC * G.K + k, ms, Vs, vs_diag != 0, (size_t)G.K);
+  if (change && !last) robust_change_max(change + k, (float)ch);
+}
+
+size_t dense_smooth_robust_workspace_bytes(int T, int K, int D, int O) {
+  const size_t base = dense_increments_workspace_bytes(T, K, D, O);   // the generic layout, with its launch-index check
+  return base ? align_up(base, 256) + align_up((size_t)T * K * O * sizeof(float), 256) : 0;
+}
+
+int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
+                        int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws,
+                        size_t ws_bytes, hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
+  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
+  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
+  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
+  if (ws_bytes < dense_smooth_robust_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
+  const int lanes = K * G.nc;
+  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
+  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
+  float* lam = weights ? weights : reinterpret_cast<float*>(static_cast<char*>(ws) + align_up(L.bytes, 256));
+  const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
+  const Gate open{nullptr, 0.0};
+  if (change) {
+    const hipError_t e = hipMemsetAsync(change, 0, (size_t)K * sizeof(float), st);
+    if (e != hipSuccess) return hip_status(e);
+  }
+  EKS_DISPATCH_D(D, {
+    for (int it = 0; it < n_iters; ++it) {
+      const int last = it == n_iters - 1;
+      const RobustObs<DD> obs = make_robust_obs<DD>(y, var, (it > 0 || weights_in) ? lam : nullptr, K, O, M);
+      dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_robust_summarize", "dense_robust_scan", st);
+      ProfScope ps("dense_robust_replay", st);
+      hipLaunchKernelGGL(dense_robust_replay_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs, lam,
+                         nu, last, it == n_iters - 2 ? change : nullptr, L.pre, L.suf, L.bprior, L.bsuffix, L.filt, ms,
+                         Vs, vs_diag);
+    }
   })
   return hip_status(hipGetLastError());
 }

@@ -157,6 +157,16 @@ int diag_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const 
 size_t dense_smooth_tv_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
                     const DenseModel& M, float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);
+// the smoother under Student-t observation noise (eks_smooth_robust.hip: scalar chains, eks_smooth_tv's shapes on
+// eks_em_stats' workspace plus a plane of weights; eks_dense.hip: general models, always the generic kernels)
+size_t diag_smooth_robust_workspace_bytes(int T, int N);
+int diag_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double nu, int n_iters,
+                       float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws, size_t ws_bytes,
+                       hipStream_t st);
+size_t dense_smooth_robust_workspace_bytes(int T, int K, int D, int O);
+int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double nu,
+                        int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws,
+                        size_t ws_bytes, hipStream_t st);
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M,
                  float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);

@@ -222,6 +222,36 @@ def smooth_tv(y, var, qscale, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool 
     return ms, Vs
 
 
+def smooth_robust(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 8, flags: int = 0, vs_diag: bool = False,
+                  weights=None, weights_in: bool = False, want_change: bool = True):
+    """eks_smooth_robust: eks_smooth under Student-t observation noise with `nu` degrees of freedom, `n_iters`
+    smoothing passes enqueued back to back (include/eks_hip.h has the model).  `weights`: a float32 device tensor
+    (T, K, O) that receives the weights; with weights_in the first pass starts from its contents.  Returns
+    (ms, Vs, weights, change): change is (K,) float32, the largest weight change of the last update (None without
+    want_change)."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
+    s = _chk(s, torch.float64, 's', (K,))
+    if weights_in and weights is None:
+        raise ValueError('weights_in needs a weights tensor')
+    if weights is None:
+        weights = torch.empty((T, K, O), dtype=torch.float32, device=y.device)
+    elif not weights.is_contiguous():
+        raise ValueError('weights must be contiguous: it is written in place')
+    weights = _chk(weights, torch.float32, 'weights', (T, K, O))
+    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
+    dims = _dims(K, T, D, O, flags)
+    ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device)
+    Vs = torch.empty((T, K, D) if vs_diag else (T, K, D, D), dtype=torch.float32, device=y.device)
+    change = torch.empty((K,), dtype=torch.float32, device=y.device) if want_change else None
+    ws = _workspace(lib.eks_smooth_robust_workspace_bytes(ctypes.byref(dims)), y.device)
+    rc = lib.eks_smooth_robust(ctypes.byref(dims), *[_ptr(b) for b in bufs], _ptr(s), float(nu), int(n_iters),
+                               _ptr(weights), int(bool(weights_in)), _ptr(change), _ptr(ms), _ptr(Vs), _ptr(ws),
+                               ws.numel(), _stream())
+    _lib.check(rc, 'eks_smooth_robust')
+    return ms, Vs, weights, change
+
+
 def smooth_increments(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False,
                       want=('lag1', 'dmean', 'dV'), want_smooth: bool = True):
     """eks_smooth_increments: eks_smooth plus lag1 = Cov(x_t, x_{t+1} | y), dmean = E[x_{t+1} - x_t | y] and

@@ -104,6 +104,42 @@ int eks_smooth_tv(const eks_dims_t* dims, const float* y, const float* var, cons
                   const double* Q, const double* s, float* ms, float* Vs, void* workspace, size_t workspace_bytes,
                   eks_stream_t stream);
 
+/* ---- eks_smooth under Student-t observation noise, for frames where the whole ensemble agrees on a wrong place (paw
+ * swaps, reflections, occlusions): small ensemble variance, wrong observation.  No reference counterpart.  For every
+ * scalar observation (chain coordinate on scalar chains, row o on general models, whose R_t is diagonal)
+ *     y_t | x_t, lam_t ~ N(C x_t, r_t / lam_t),    lam_t ~ Gamma(nu / 2, rate nu / 2),    r_t = clip(var_t),
+ * with eks_smooth's dynamics; inference is the mean-field iteration of Agamennoni, Nieto and Nebot (2012).  A call runs
+ * n_iters >= 1 smoothing passes, all enqueued back to back.  Every pass smooths under r_eff = clip(r_t / lam_t); every
+ * pass but the last then sets lam_t = (nu + 1) / (nu + delta_t), delta_t = ((y_t - C ms_t)^2 + C Vs_t C') / r_t (the
+ * full Vs on general models), in (0, (nu + 1) / nu].  The last pass writes ms, Vs and leaves the weights alone: the
+ * weights returned are the ones ms, Vs were smoothed under.  n_iters = 1 without input weights is eks_smooth's model
+ * (on scalar chains: eks_smooth_tv's bits at w = 1).  A frame with var = 1e30 stays effectively missing.
+ * dims, flags, y, var, the parameters and the layouts of ms and Vs are exactly those of eks_smooth.
+ *   nu          degrees of freedom, finite and > 0 (large nu: the Gaussian smoother).
+ *   weights     float32 [T][K][O], frame-major like var; may be NULL (a plane of the workspace serves: the size query
+ *               always includes one).  weights_in != 0: the first pass starts from the caller's values (each finite
+ *               and > 0) instead of 1 - to continue a run, or for a single pass under weights the caller chose; needs
+ *               a non-NULL weights (else EKS_ERR_NULL).  Without it the plane is not read before it is written.
+ *   change      float32 [K], may be NULL: max over frames and coordinates of |lam_new - lam_old| in the call's last
+ *               weight update (an atomic max on the bits of non-negative floats, as eks_ekf_smooth's resid).  The call
+ *               zeroes it first; it stays zero when n_iters = 1.
+ *   scalar chains   float32 lanes, five launches per pass: a summarize and a replay of their own around eks_em_stats'
+ *               three-launch scan; workspace as eks_em_stats plus the plane and a [T] vector of ones (the frames run
+ *               eks_smooth_tv's bodies at w = 1).  Never the windowed replay.
+ *   general models  D <= 6 and O <= 64 (else EKS_ERR_UNSUPPORTED and a workspace size of 0); always the generic
+ *               float64 summarize / scan / replay kernels.  Correct, not tuned.
+ *   accuracy    y - C ms cancels in float32 on scalar chains, so delta carries an absolute error of about
+ *               (2^-24 |y|)^2 / r: negligible for var >= 1e-2 at |y| <= 400 px, useless for var near the 1e-12 clip -
+ *               there the weights stay finite and in range (floored at 1e-30) but mean nothing.
+ * Refusals are eks_smooth_tv's plus EKS_ERR_SHAPE for a non-finite or non-positive nu and for n_iters < 1; all are
+ * returned before anything is enqueued and leave every output untouched.  The size query returns 0 for refused
+ * shapes. ------------------ */
+size_t eks_smooth_robust_workspace_bytes(const eks_dims_t* dims);
+int eks_smooth_robust(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,
+                      const double* A, const double* C, const double* Q, const double* s, double nu, int32_t n_iters,
+                      float* weights, int32_t weights_in, float* change, float* ms, float* Vs, void* workspace,
+                      size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- joint posterior trajectories: n_draws draws of x_1..x_T from the smoothing distribution p(x | y) of the model
  * eks_smooth smooths (same dims, flags, y, var and parameters; EKS_FLAG_VS_DIAG is ignored).  No reference counterpart:
  * the reference returns the per-frame marginals ms, Vs only (eks/core.py:296-297), which say nothing about how the
