@@ -27,6 +27,7 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'process_noise_scale_from_times': 'irregular', 'smooth_time_varying': 'irregular',
         'smooth_singlecam_irregular': 'irregular',
         'smooth_robust': 'robust', 'smooth_singlecam_robust': 'robust',
+        'smooth_jumps': 'jumps', 'smooth_singlecam_jumps': 'jumps',
     }
     if name in table:
         return getattr(importlib.import_module(f'.{table[name]}', __name__), name)

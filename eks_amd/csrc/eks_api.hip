@@ -123,6 +123,34 @@ int eks_smooth_robust(const eks_dims_t* d, const float* y, const float* var, con
                              workspace_bytes, st);
 }
 
+size_t eks_smooth_jumps_workspace_bytes(const eks_dims_t* d) {
+  if (smooth_tv_check(d) != EKS_OK) return 0;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_smooth_jumps_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim);
+  return dense_smooth_jumps_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+}
+
+int eks_smooth_jumps(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
+                     const double* A, const double* C, const double* Q, const double* s, double nu, int32_t n_iters,
+                     float* scales, int32_t scales_in, float* change, float* ms, float* Vs, void* workspace,
+                     size_t workspace_bytes, eks_stream_t stream) {
+  const int rc = smooth_tv_check(d);   // eks_smooth_tv's shapes and refusals
+  if (rc != EKS_OK) return rc;
+  if (!(nu > 0.0) || !(nu <= 1.7e308) || n_iters < 1) return EKS_ERR_SHAPE;
+  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s || !ms || !Vs) return EKS_ERR_NULL;
+  if (scales_in && !scales) return EKS_ERR_NULL;
+  if (!workspace) return EKS_ERR_WORKSPACE;
+  if (workspace_bytes < eks_smooth_jumps_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (d->flags & EKS_FLAG_DIAG_MODEL) {
+    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
+    return diag_smooth_jumps(*d, y, var, M, nu, n_iters, scales, scales_in, change, ms, Vs, workspace, workspace_bytes,
+                             st);
+  }
+  const DenseModel M{m0, S0, A, C, Q, s};
+  return dense_smooth_jumps(*d, y, var, M, nu, n_iters, scales, scales_in, change, ms, Vs, workspace, workspace_bytes,
+                            st);
+}
+
 // shapes eks_smooth_increments takes (EKS_OK) or the status it refuses them with; nothing here touches the device
 static int increments_check(const eks_dims_t* d) {
   const int rc = check_dims(d);

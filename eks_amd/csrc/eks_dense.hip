@@ -20,6 +20,7 @@
 #include "eks_increments_lane.hpp"
 #include "eks_innov_lane.hpp"
 #include "eks_internal.hpp"
+#include "eks_smooth_jumps_lane.hpp"
 #include "eks_smooth_robust_lane.hpp"
 #include "eks_smooth_tv_lane.hpp"
 
@@ -628,6 +629,84 @@ int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, c
     }
   })
   return hip_status(hipGetLastError());
+}
+
+// ---- eks_smooth_jumps on general models: n_iters passes of dense_smooth_tv's organisation under the scale plane -------
+// A middle pass: dense_tv_summarize_kernel -> dense_scan -> dense_scan_blocks as they are, a replay of its own
+// (eks_smooth_jumps_lane.hpp: dense_jumps_replay_chunk) that writes delta_t into a [T][K] float64 plane, and
+// eks_smooth_jumps.hip's combine launch, the only one that changes the scales.  The last pass is dense_smooth_tv itself.
+template <int D>
+__global__ __launch_bounds__(64) void dense_jumps_replay_kernel(DenseGeom G, DenseModelPtrs M,
+                                                               const double* __restrict__ s, LinearObs<D> obs,
+                                                               const float* __restrict__ scales,
+                                                               const double* __restrict__ pre,
+                                                               const double* __restrict__ suf,
+                                                               const double* __restrict__ bprior,
+                                                               const double* __restrict__ bsuffix,
+                                                               double* __restrict__ filt, double* __restrict__ delta) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.nc) return;
+  constexpr int REC = D + D * D;
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  const DenseNoiseScale ns{scales, G.K, k};
+  Vec<double, D> m, eta;
+  Mat<double, D> P, J;
+  dense_chunk_boundary<D>(G, M, k, j, j, pre, suf, bprior, bsuffix, m, P, eta, J);   // one element per lane (Bs == B)
+  const int t0 = j * G.B, len = min(G.B, G.T - t0);
+  dense_jumps_replay_chunk<D>(obs, ns, G.K, k, t0, len, F, sQ, fid, m, P, eta, J, filt + (size_t)t0 * REC * G.K + k,
+                              delta, (size_t)G.K);
+}
+
+static size_t dense_jumps_plane_bytes(int T, int K, size_t elem) { return align_up((size_t)T * K * elem, 256); }
+size_t dense_smooth_jumps_workspace_bytes(int T, int K, int D, int O) {
+  const size_t base = dense_smooth_tv_workspace_bytes(T, K, D, O);   // the generic layout, with its launch-index check
+  return base ? align_up(base, 256) + dense_jumps_plane_bytes(T, K, sizeof(float)) +
+                    dense_jumps_plane_bytes(T, K, sizeof(double))
+              : 0;
+}
+
+int dense_smooth_jumps(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
+                       int n_iters, float* scales, int scales_in, float* change, float* ms, float* Vs, void* ws,
+                       size_t ws_bytes, hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
+  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
+  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
+  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
+  if (ws_bytes < dense_smooth_jumps_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
+  const int lanes = K * G.nc;
+  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
+  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
+  char* tail = static_cast<char*>(ws) + align_up(dense_smooth_tv_workspace_bytes(T, K, D, O), 256);
+  float* plane = scales ? scales : reinterpret_cast<float*>(tail);
+  double* delta = reinterpret_cast<double*>(tail + dense_jumps_plane_bytes(T, K, sizeof(float)));
+  int rc = jumps_init_plane(plane, T, K, scales_in, change, st);
+  if (rc != EKS_OK) return rc;
+  const Gate open{nullptr, 0.0};
+  EKS_DISPATCH_D(D, {
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
+    for (int it = 0; it + 1 < n_iters; ++it) {
+      {
+        ProfScope ps("dense_jumps_summarize", st);
+        hipLaunchKernelGGL(dense_tv_summarize_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs,
+                           plane, 1, L.elems, L.first);
+      }
+      {
+        ProfScope ps("dense_jumps_scan", st);
+        dense_scan_launch<DD>(G, L, open, st);
+      }
+      {
+        ProfScope ps("dense_jumps_replay", st);
+        hipLaunchKernelGGL(dense_jumps_replay_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs, plane,
+                           L.pre, L.suf, L.bprior, L.bsuffix, L.filt, delta);
+      }
+      rc = jumps_combine(delta, true, 1, plane, it == n_iters - 2 ? change : nullptr, T, K, nu, D, st);
+      if (rc != EKS_OK) return rc;
+    }
+  })
+  return dense_smooth_tv(d, y, var, plane, 1, Mm, ms, Vs, ws, ws_bytes, st);
 }
 
 // ---- eks_em_stats on general models: dense_increments' organisation with the outputs replaced by a sum -----------

@@ -167,6 +167,20 @@ size_t dense_smooth_robust_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double nu,
                         int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws,
                         size_t ws_bytes, hipStream_t st);
+// the smoother under Student-t process noise (eks_smooth_jumps.hip: scalar chains, eks_smooth_tv's shapes on
+// eks_em_stats' workspace plus a scale and a contribution plane, and the combine launch both paths share;
+// eks_dense.hip: general models, always the generic kernels)
+size_t diag_smooth_jumps_workspace_bytes(int T, int K, int D);
+int diag_smooth_jumps(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double nu, int n_iters,
+                      float* scales, int scales_in, float* change, float* ms, float* Vs, void* ws, size_t ws_bytes,
+                      hipStream_t st);
+size_t dense_smooth_jumps_workspace_bytes(int T, int K, int D, int O);
+int dense_smooth_jumps(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double nu,
+                       int n_iters, float* scales, int scales_in, float* change, float* ms, float* Vs, void* ws,
+                       size_t ws_bytes, hipStream_t st);
+int jumps_init_plane(float* plane, int T, int K, int scales_in, float* change, hipStream_t st);
+int jumps_combine(const void* contrib, bool f64, int nd, float* scales, float* change, int T, int K, double nu, int D,
+                  hipStream_t st);
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M,
                  float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);

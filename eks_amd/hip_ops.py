@@ -252,6 +252,36 @@ def smooth_robust(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 8,
     return ms, Vs, weights, change
 
 
+def smooth_jumps(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 12, flags: int = 0, vs_diag: bool = False,
+                 scales=None, scales_in: bool = False, want_change: bool = True):
+    """eks_smooth_jumps: eks_smooth under Student-t process noise with `nu` degrees of freedom, one scale per frame
+    and keypoint, `n_iters` smoothing passes enqueued back to back (include/eks_hip.h has the model).  `scales`: a
+    float32 device tensor (T, K) that receives the scales - eks_smooth_tv's per-keypoint qscale; with scales_in the
+    first pass starts from its contents.  Returns (ms, Vs, scales, change): change is (K,) float32, the largest
+    change of u = 1 / scale in the last update (None without want_change)."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
+    s = _chk(s, torch.float64, 's', (K,))
+    if scales_in and scales is None:
+        raise ValueError('scales_in needs a scales tensor')
+    if scales is None:
+        scales = torch.empty((T, K), dtype=torch.float32, device=y.device)
+    elif not scales.is_contiguous():
+        raise ValueError('scales must be contiguous: it is written in place')
+    scales = _chk(scales, torch.float32, 'scales', (T, K))
+    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
+    dims = _dims(K, T, D, O, flags)
+    ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device)
+    Vs = torch.empty((T, K, D) if vs_diag else (T, K, D, D), dtype=torch.float32, device=y.device)
+    change = torch.empty((K,), dtype=torch.float32, device=y.device) if want_change else None
+    ws = _workspace(lib.eks_smooth_jumps_workspace_bytes(ctypes.byref(dims)), y.device)
+    rc = lib.eks_smooth_jumps(ctypes.byref(dims), *[_ptr(b) for b in bufs], _ptr(s), float(nu), int(n_iters),
+                              _ptr(scales), int(bool(scales_in)), _ptr(change), _ptr(ms), _ptr(Vs), _ptr(ws),
+                              ws.numel(), _stream())
+    _lib.check(rc, 'eks_smooth_jumps')
+    return ms, Vs, scales, change
+
+
 def smooth_increments(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False,
                       want=('lag1', 'dmean', 'dV'), want_smooth: bool = True):
     """eks_smooth_increments: eks_smooth plus lag1 = Cov(x_t, x_{t+1} | y), dmean = E[x_{t+1} - x_t | y] and

@@ -140,6 +140,50 @@ int eks_smooth_robust(const eks_dims_t* dims, const float* y, const float* var, 
                       float* weights, int32_t weights_in, float* change, float* ms, float* Vs, void* workspace,
                       size_t workspace_bytes, eks_stream_t stream);
 
+/* ---- eks_smooth under Student-t PROCESS noise, for true fast movements (a paw reach, a saccade, a startle): a few
+ * frames of motion far larger than the rest of the session, which one s per keypoint must either round off or follow
+ * at the price of under-smoothing every still frame.  No reference counterpart.  One weight per keypoint and frame,
+ * shared by its D state coordinates (they jump together):
+ *     x_t = A x_{t-1} + eps_t,   eps_t | u_t ~ N(0, s Q / u_t),   u_t ~ Gamma(nu / 2, rate nu / 2),   t = 1 .. T-1,
+ * with eks_smooth's prior and observations; inference is the mean-field iteration.  A call runs n_iters >= 1 smoothing
+ * passes, all enqueued back to back.  Every pass smooths under the scales w_t = 1 / u_t - exactly eks_smooth_tv with
+ * qscale_per_keypoint = 1; every pass but the last then sets w_t = (nu + delta_t) / (nu + D),
+ * delta_t = E[eps_t' (s Q)^-1 eps_t | y] under the pass's own scales, formed from what the RTS step holds without
+ * inverting Q (singular Q is fine on general models); u stays in [1e-30, (nu + D) / nu].  The last pass writes ms, Vs
+ * and leaves the scales alone: the scales returned are the ones ms, Vs were smoothed under (bit for bit eks_smooth_tv
+ * called with them).  n_iters = 1 without input scales is eks_smooth_tv at w = 1.
+ * dims, flags, y, var, the parameters and the layouts of ms and Vs are exactly those of eks_smooth_tv.
+ *   nu          degrees of freedom, finite and > 0 (large nu: the Gaussian smoother).
+ *   scales      float32 [T][K], the layout of eks_smooth_tv's per-keypoint qscale: w of the step INTO frame t; may be
+ *               NULL (a plane of the workspace serves: the size query always includes one).  Row 0 is never read and is
+ *               returned as 1.  scales_in != 0: the first pass starts from the caller's values (each finite and > 0)
+ *               instead of 1 - to continue a run, or for a single pass under scales the caller chose; needs a non-NULL
+ *               scales (else EKS_ERR_NULL).
+ *   change      float32 [K], may be NULL: max over frames of |u_new - u_old|, u = 1 / w, in the call's last scale
+ *               update (an atomic max on the bits of non-negative floats).  The call zeroes it first; it stays zero
+ *               when n_iters = 1.
+ *   continuing  n1 passes continued (scales_in) by n2 passes are one call of n1 + n2 - 1 passes, bit for bit.
+ *   scalar chains   float32 lanes.  A middle pass is six launches: eks_smooth_tv's summarize, eks_em_stats'
+ *               three-launch scan, a replay without outputs that stores every chain's delta_{t,d} into a [T][K D]
+ *               plane, and a combine launch - the only one that changes the scales, because the D chains of a keypoint
+ *               sit in different lanes.  The last pass is eks_smooth_tv's five launches.  Workspace: eks_em_stats' plus
+ *               the two planes.  Never the windowed replay.  A chain with s q = 0 contributes w_t, its prior value
+ *               (never 0 / 0), so a keypoint whose chains all have s q = 0 keeps w = 1.
+ *   general models  D <= 6 and O <= 64 (else EKS_ERR_UNSUPPORTED and a workspace size of 0); always the generic
+ *               float64 summarize / scan / replay kernels, delta_t in a [T][K] float64 plane, the same combine launch.
+ *   accuracy    dm = ms_t - a mf_{t-1} cancels in float32 on scalar chains as y - c ms does for eks_smooth_robust's
+ *               weights: delta carries an absolute error of about (2^-24 |ms|)^2 / Pp - negligible for s q >= 1e-3 at
+ *               |y| <= 400 px, growing as s q and var fall towards their floors, where the scales stay finite and in
+ *               range but mean little.
+ * Refusals are eks_smooth_tv's plus EKS_ERR_SHAPE for a non-finite or non-positive nu and for n_iters < 1; all are
+ * returned before anything is enqueued and leave every output untouched.  The size query returns 0 for refused
+ * shapes. ------------------ */
+size_t eks_smooth_jumps_workspace_bytes(const eks_dims_t* dims);
+int eks_smooth_jumps(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,
+                     const double* A, const double* C, const double* Q, const double* s, double nu, int32_t n_iters,
+                     float* scales, int32_t scales_in, float* change, float* ms, float* Vs, void* workspace,
+                     size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- joint posterior trajectories: n_draws draws of x_1..x_T from the smoothing distribution p(x | y) of the model
  * eks_smooth smooths (same dims, flags, y, var and parameters; EKS_FLAG_VS_DIAG is ignored).  No reference counterpart:
  * the reference returns the per-frame marginals ms, Vs only (eks/core.py:296-297), which say nothing about how the
