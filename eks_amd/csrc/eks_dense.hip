@@ -10,6 +10,10 @@
 //   D3 dense_replay    : lane = (keypoint, chunk): exact filter, fuse, RTS; filtered beliefs go
 //                        through a per-lane scratch record stream (these problems are tiny:
 //                        BASELINE config 4 is 4 keypoints x 50k frames, latency- not HBM-bound)
+// Six more features run D1 -> D2 -> a replay kernel of their own on this organisation (increments, tv, robust, jumps,
+// EM statistics, innovations).  Their host side is written once: checks, layout and tail (DensePass, dense_pass_begin,
+// dense_generic_workspace_bytes) and the launches (dense_prelude, dense_tv_prelude, dense_pass_launch).  The kernels'
+// opening lines are not shared, on measurement: DESIGN.md 9k.
 // The losses of this path (eks_nll, eks_ar1_nll) live in eks_loss_kernels.hpp.
 #include <hip/hip_runtime.h>
 
@@ -339,12 +343,64 @@ static void dense_prelude(const DenseGeom& G, const DenseModelPtrs& M, const dou
                           const char* scan_scope, hipStream_t st) {
   {
     ProfScope ps(summarize_scope, st);
-    hipLaunchKernelGGL((dense_summarize_kernel<D, Obs>), dim3((G.K * G.ncs + 63) / 64), dim3(64), 0, st, G, M, s, obs,
-                       L.elems, L.first, gate);
+    hipLaunchKernelGGL((dense_summarize_kernel<D, Obs>), dim3((G.K * G.ncs + 63) / 64), dim3(64), 0, st, G, M, s,
+                       obs, L.elems, L.first, gate);
   }
   ProfScope ps(scan_scope, st);
   dense_scan_launch<D>(G, L, gate, st);
 }
+
+// ---- the features that always take the generic organisation (correct first, like the dense sampler, whatever
+// dense_path would pick for eks_smooth): increments, tv, robust, jumps, EM statistics, innovations ------------------
+// Each is dense_pass_begin, dense_prelude and one dense_pass_launch of its replay kernel (that pair per iteration for
+// the iterated ones); its workspace is the generic layout - with the filtered-belief stream over `filt_frames` frames:
+// T, or 0 for a forward-only pass - and a tail of its own behind it.
+static int dense_nc(int T, int K) {
+  const int B = dense_chunk(T, K);
+  return (T + B - 1) / B;
+}
+static size_t dense_plane_bytes(size_t count, size_t elem) { return align_up(count * elem, 256); }
+
+// 0 where dense_pass_begin refuses the shape.
+static size_t dense_generic_workspace_bytes(int filt_frames, int K, int D, int O, int T, size_t tail_bytes) {
+  if (D < 1 || D > 6 || O < 1 || O > 64) return 0;
+  const int nc = dense_nc(T, K);
+  if ((long long)K * nc >= (1 << 30)) return 0;
+  return generic_layout(filt_frames, K, D, nc, nullptr).bytes + tail_bytes;   // (the layout ends 256-aligned)
+}
+
+struct DensePass {
+  DenseGeom G;
+  DenseModelPtrs M;
+  const double* s;
+  GenericLayout L;
+  int lanes;
+  char* tail;       // the pass's own region behind the layout
+};
+static int dense_pass_begin(const eks_dims_t& d, const DenseModel& Mm, int filt_frames, size_t tail_bytes, void* ws,
+                            size_t ws_bytes, DensePass& P) {
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
+  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
+  P.G = dense_geom(T, K, O, dense_chunk(T, K));
+  if ((long long)K * P.G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
+  P.L = generic_layout(filt_frames, K, D, P.G.nc, static_cast<char*>(ws));
+  if (ws_bytes < P.L.bytes + tail_bytes) return EKS_ERR_WORKSPACE;
+  P.M = DenseModelPtrs{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
+  P.s = Mm.s;
+  P.lanes = K * P.G.nc;
+  P.tail = static_cast<char*>(ws) + P.L.bytes;
+  return EKS_OK;
+}
+
+// One launch of a replay kernel, lane = (keypoint, chunk), under its profile scope (a string literal: ProfScope keeps
+// the pointer).  `args`: the kernel's arguments after (G, M, s).
+template <typename... KArgs, typename... Args>
+static void dense_pass_launch(const DensePass& P, const char* scope, hipStream_t st, void (*kernel)(KArgs...),
+                              const Args&... args) {
+  ProfScope ps(scope, st);
+  kernel<<<dim3((P.lanes + 63) / 64), dim3(64), 0, st>>>(P.G, P.M, P.s, args...);
+}
+constexpr Gate kGateOpen{nullptr, 0.0};
 
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O) {
   const int B = dense_chunk(T, K), nc = (T + B - 1) / B;
@@ -417,10 +473,7 @@ int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const De
   return hip_status(hipGetLastError());
 }
 
-// ---- eks_smooth_increments on general models: a third mode of the generic organisation ---------------------
-// dense_summarize -> dense_scan -> dense_scan_blocks as they are, then a replay that also emits lag1, dmean and dV
-// (eks_increments_lane.hpp: dense_increments_chunk).  Always the generic kernels and their workspace layout, whatever
-// dense_path would pick for eks_smooth: correct first, like the dense sampler.
+// ---- eks_smooth_increments: a replay that also emits lag1, dmean and dV (eks_increments_lane.hpp) -------------------
 template <int D, typename Obs>
 __global__ __launch_bounds__(64) void dense_increments_kernel(DenseGeom G, DenseModelPtrs M,
                                                              const double* __restrict__ s, Obs obs,
@@ -445,40 +498,26 @@ __global__ __launch_bounds__(64) void dense_increments_kernel(DenseGeom G, Dense
 }
 
 size_t dense_increments_workspace_bytes(int T, int K, int D, int O) {
-  if (D < 1 || D > 6 || O < 1 || O > 64) return 0;
-  const int B = dense_chunk(T, K), nc = (T + B - 1) / B;
-  if ((long long)K * nc >= (1 << 30)) return 0;   // dense_increments: EKS_ERR_SHAPE
-  return generic_layout(T, K, D, nc, nullptr).bytes;
+  return dense_generic_workspace_bytes(T, K, D, O, T, 0);
 }
 
 int dense_increments(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, float* ms, float* Vs,
                      float* lag1, float* dmean, float* dV, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
-  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
-  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
-  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
-  if (ws_bytes < dense_increments_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
-  const int lanes = K * G.nc;
-  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
-  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
-  const DenseIncrementsOut out{ms, Vs, lag1, dmean, dV, (d.flags & EKS_FLAG_VS_DIAG) != 0, T};
-  const Gate open{nullptr, 0.0};
-  EKS_DISPATCH_D(D, {
-    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
-    dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_increments_summarize", "dense_increments_scan", st);
-    {
-      ProfScope ps("dense_increments_replay", st);
-      hipLaunchKernelGGL((dense_increments_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M,
-                         Mm.s, obs, L.pre, L.suf, L.bprior, L.bsuffix, L.filt, out);
-    }
+  DensePass P;
+  const int rc = dense_pass_begin(d, Mm, d.n_frames, 0, ws, ws_bytes, P);
+  if (rc != EKS_OK) return rc;
+  const DenseIncrementsOut out{ms, Vs, lag1, dmean, dV, (d.flags & EKS_FLAG_VS_DIAG) != 0, d.n_frames};
+  EKS_DISPATCH_D(d.state_dim, {
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, P.G.K, P.G.O, P.M);
+    dense_prelude<DD>(P.G, P.M, P.s, obs, P.L, kGateOpen, "dense_increments_summarize", "dense_increments_scan", st);
+    dense_pass_launch(P, "dense_increments_replay", st, dense_increments_kernel<DD, LinearObs<DD>>, obs, P.L.pre,
+                      P.L.suf, P.L.bprior, P.L.bsuffix, P.L.filt, out);
   })
   return hip_status(hipGetLastError());
 }
 
-// ---- eks_smooth_tv on general models: the generic organisation with w_t s Q per frame --------------------------------
-// Summarize and replay of their own (eks_smooth_tv_lane.hpp: dense_tv_element, dense_tv_replay_chunk) around
-// dense_scan -> dense_scan_blocks as they are - the scan composes elements and never sees Q.  Always the generic kernels
-// and their workspace layout, whatever dense_path would pick for eks_smooth: correct first, like the dense sampler.
+// ---- eks_smooth_tv: w_t s Q per frame in summarize and replay (eks_smooth_tv_lane.hpp: dense_tv_element,
+// dense_tv_replay_chunk); the scan composes elements and never sees Q ------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(64) void dense_tv_summarize_kernel(DenseGeom G, DenseModelPtrs M,
                                                                const double* __restrict__ s, LinearObs<D> obs,
@@ -501,6 +540,16 @@ __global__ __launch_bounds__(64) void dense_tv_summarize_kernel(DenseGeom G, Den
     belief_update_obs<D>(obs, k, 0, nullptr, m, P);
     dense_store_rec<D>(first + (size_t)k * (D + D * D), 1, m, P);
   }
+}
+
+// dense_prelude under the scale plane qscale: [T] shared, or [T][K] per keypoint.
+template <int D>
+static void dense_tv_prelude(const DensePass& P, const LinearObs<D>& obs, const float* qscale, int per_keypoint,
+                             const char* summarize_scope, const char* scan_scope, hipStream_t st) {
+  dense_pass_launch(P, summarize_scope, st, dense_tv_summarize_kernel<D>, obs, qscale, per_keypoint, P.L.elems,
+                    P.L.first);
+  ProfScope ps(scan_scope, st);
+  dense_scan_launch<D>(P.G, P.L, kGateOpen, st);
 }
 
 template <int D>
@@ -530,44 +579,28 @@ __global__ __launch_bounds__(64) void dense_tv_replay_kernel(DenseGeom G, DenseM
 }
 
 size_t dense_smooth_tv_workspace_bytes(int T, int K, int D, int O) {
-  return dense_increments_workspace_bytes(T, K, D, O);   // the generic layout, with the same launch-index check
+  return dense_generic_workspace_bytes(T, K, D, O, T, 0);
 }
 
 int dense_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
                     const DenseModel& Mm, float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
-  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
-  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
-  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
-  if (ws_bytes < dense_smooth_tv_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
-  const int lanes = K * G.nc;
-  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
-  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
+  DensePass P;
+  const int rc = dense_pass_begin(d, Mm, d.n_frames, 0, ws, ws_bytes, P);
+  if (rc != EKS_OK) return rc;
   const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0, pk = per_keypoint ? 1 : 0;
-  const Gate open{nullptr, 0.0};
-  EKS_DISPATCH_D(D, {
-    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
-    {
-      ProfScope ps("dense_tv_summarize", st);
-      hipLaunchKernelGGL(dense_tv_summarize_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs, qscale,
-                         pk, L.elems, L.first);
-    }
-    {
-      ProfScope ps("dense_tv_scan", st);
-      dense_scan_launch<DD>(G, L, open, st);
-    }
-    ProfScope ps("dense_tv_replay", st);
-    hipLaunchKernelGGL(dense_tv_replay_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs, qscale, pk,
-                       L.pre, L.suf, L.bprior, L.bsuffix, L.filt, ms, Vs, vs_diag);
+  EKS_DISPATCH_D(d.state_dim, {
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, P.G.K, P.G.O, P.M);
+    dense_tv_prelude<DD>(P, obs, qscale, pk, "dense_tv_summarize", "dense_tv_scan", st);
+    dense_pass_launch(P, "dense_tv_replay", st, dense_tv_replay_kernel<DD>, obs, qscale, pk, P.L.pre, P.L.suf,
+                      P.L.bprior, P.L.bsuffix, P.L.filt, ms, Vs, vs_diag);
   })
   return hip_status(hipGetLastError());
 }
 
-// ---- eks_smooth_robust on general models: n_iters passes of the generic organisation under r / lam -------------------
-// dense_summarize -> dense_scan -> dense_scan_blocks as they are on an observation source that divides r by
-// lam[t][k][o] (eks_smooth_robust_lane.hpp: RobustObs), then a replay of its own that updates the weights in place
-// (middle passes) or writes ms, Vs (the last).  Correct, not tuned: always the generic kernels and their layout, with
-// one [T][K][O] float plane of weights behind it.
+// ---- eks_smooth_robust: n_iters passes under r / lam ----------------------------------------------------------------
+// The prelude runs on an observation source that divides r by lam[t][k][o] (eks_smooth_robust_lane.hpp: RobustObs); the
+// replay updates the weights in place (middle passes) or writes ms, Vs (the last).  Tail: one [T][K][O] float plane of
+// weights, used when the caller passes none.
 template <int D>
 __global__ __launch_bounds__(64) void dense_robust_replay_kernel(DenseGeom G, DenseModelPtrs M,
                                                                 const double* __restrict__ s, RobustObs<D> obs,
@@ -594,47 +627,44 @@ __global__ __launch_bounds__(64) void dense_robust_replay_kernel(DenseGeom G, De
   if (change && !last) robust_change_max(change + k, (float)ch);
 }
 
+static size_t dense_robust_tail_bytes(int T, int K, int O) {
+  return dense_plane_bytes((size_t)T * K * O, sizeof(float));
+}
 size_t dense_smooth_robust_workspace_bytes(int T, int K, int D, int O) {
-  const size_t base = dense_increments_workspace_bytes(T, K, D, O);   // the generic layout, with its launch-index check
-  return base ? align_up(base, 256) + align_up((size_t)T * K * O * sizeof(float), 256) : 0;
+  return dense_generic_workspace_bytes(T, K, D, O, T, dense_robust_tail_bytes(T, K, O));
 }
 
 int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
                         int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws,
                         size_t ws_bytes, hipStream_t st) {
-  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
-  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
-  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
-  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
-  if (ws_bytes < dense_smooth_robust_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
-  const int lanes = K * G.nc;
-  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
-  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
-  float* lam = weights ? weights : reinterpret_cast<float*>(static_cast<char*>(ws) + align_up(L.bytes, 256));
+  const int T = d.n_frames, K = d.n_keypoints, O = d.obs_dim;
+  DensePass P;
+  const int rc = dense_pass_begin(d, Mm, T, dense_robust_tail_bytes(T, K, O), ws, ws_bytes, P);
+  if (rc != EKS_OK) return rc;
+  float* lam = weights ? weights : reinterpret_cast<float*>(P.tail);
   const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
-  const Gate open{nullptr, 0.0};
   if (change) {
     const hipError_t e = hipMemsetAsync(change, 0, (size_t)K * sizeof(float), st);
     if (e != hipSuccess) return hip_status(e);
   }
-  EKS_DISPATCH_D(D, {
+  EKS_DISPATCH_D(d.state_dim, {
     for (int it = 0; it < n_iters; ++it) {
       const int last = it == n_iters - 1;
-      const RobustObs<DD> obs = make_robust_obs<DD>(y, var, (it > 0 || weights_in) ? lam : nullptr, K, O, M);
-      dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_robust_summarize", "dense_robust_scan", st);
-      ProfScope ps("dense_robust_replay", st);
-      hipLaunchKernelGGL(dense_robust_replay_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs, lam,
-                         nu, last, it == n_iters - 2 ? change : nullptr, L.pre, L.suf, L.bprior, L.bsuffix, L.filt, ms,
-                         Vs, vs_diag);
+      const RobustObs<DD> obs = make_robust_obs<DD>(y, var, (it > 0 || weights_in) ? lam : nullptr, K, O, P.M);
+      dense_prelude<DD>(P.G, P.M, P.s, obs, P.L, kGateOpen, "dense_robust_summarize", "dense_robust_scan", st);
+      dense_pass_launch(P, "dense_robust_replay", st, dense_robust_replay_kernel<DD>, obs, lam, nu, last,
+                        it == n_iters - 2 ? change : nullptr, P.L.pre, P.L.suf, P.L.bprior, P.L.bsuffix, P.L.filt, ms,
+                        Vs, vs_diag);
     }
   })
   return hip_status(hipGetLastError());
 }
 
-// ---- eks_smooth_jumps on general models: n_iters passes of dense_smooth_tv's organisation under the scale plane -------
-// A middle pass: dense_tv_summarize_kernel -> dense_scan -> dense_scan_blocks as they are, a replay of its own
-// (eks_smooth_jumps_lane.hpp: dense_jumps_replay_chunk) that writes delta_t into a [T][K] float64 plane, and
-// eks_smooth_jumps.hip's combine launch, the only one that changes the scales.  The last pass is dense_smooth_tv itself.
+// ---- eks_smooth_jumps: n_iters passes of dense_smooth_tv's organisation under the scale plane -----------------------
+// A middle pass: the prelude under the plane, a replay (eks_smooth_jumps_lane.hpp) that writes delta_t into a [T][K]
+// float64 plane, and eks_smooth_jumps.hip's combine launch, the only one that changes the scales.  The last pass is
+// dense_smooth_tv itself, on the front of the same workspace.  Tail: the [T][K] float scale plane (used when the caller
+// passes none), then the delta plane.
 template <int D>
 __global__ __launch_bounds__(64) void dense_jumps_replay_kernel(DenseGeom G, DenseModelPtrs M,
                                                                const double* __restrict__ s, LinearObs<D> obs,
@@ -660,59 +690,41 @@ __global__ __launch_bounds__(64) void dense_jumps_replay_kernel(DenseGeom G, Den
                               delta, (size_t)G.K);
 }
 
-static size_t dense_jumps_plane_bytes(int T, int K, size_t elem) { return align_up((size_t)T * K * elem, 256); }
+static size_t dense_jumps_scale_bytes(int T, int K) { return dense_plane_bytes((size_t)T * K, sizeof(float)); }
+static size_t dense_jumps_tail_bytes(int T, int K) {
+  return dense_jumps_scale_bytes(T, K) + dense_plane_bytes((size_t)T * K, sizeof(double));
+}
 size_t dense_smooth_jumps_workspace_bytes(int T, int K, int D, int O) {
-  const size_t base = dense_smooth_tv_workspace_bytes(T, K, D, O);   // the generic layout, with its launch-index check
-  return base ? align_up(base, 256) + dense_jumps_plane_bytes(T, K, sizeof(float)) +
-                    dense_jumps_plane_bytes(T, K, sizeof(double))
-              : 0;
+  return dense_generic_workspace_bytes(T, K, D, O, T, dense_jumps_tail_bytes(T, K));
 }
 
 int dense_smooth_jumps(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
                        int n_iters, float* scales, int scales_in, float* change, float* ms, float* Vs, void* ws,
                        size_t ws_bytes, hipStream_t st) {
-  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
-  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
-  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
-  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
-  if (ws_bytes < dense_smooth_jumps_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
-  const int lanes = K * G.nc;
-  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
-  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
-  char* tail = static_cast<char*>(ws) + align_up(dense_smooth_tv_workspace_bytes(T, K, D, O), 256);
-  float* plane = scales ? scales : reinterpret_cast<float*>(tail);
-  double* delta = reinterpret_cast<double*>(tail + dense_jumps_plane_bytes(T, K, sizeof(float)));
-  int rc = jumps_init_plane(plane, T, K, scales_in, change, st);
+  const int T = d.n_frames, K = d.n_keypoints;
+  DensePass P;
+  int rc = dense_pass_begin(d, Mm, T, dense_jumps_tail_bytes(T, K), ws, ws_bytes, P);
   if (rc != EKS_OK) return rc;
-  const Gate open{nullptr, 0.0};
-  EKS_DISPATCH_D(D, {
-    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
+  float* plane = scales ? scales : reinterpret_cast<float*>(P.tail);
+  double* delta = reinterpret_cast<double*>(P.tail + dense_jumps_scale_bytes(T, K));
+  rc = jumps_init_plane(plane, T, K, scales_in, change, st);
+  if (rc != EKS_OK) return rc;
+  EKS_DISPATCH_D(d.state_dim, {
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, P.G.O, P.M);
     for (int it = 0; it + 1 < n_iters; ++it) {
-      {
-        ProfScope ps("dense_jumps_summarize", st);
-        hipLaunchKernelGGL(dense_tv_summarize_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs,
-                           plane, 1, L.elems, L.first);
-      }
-      {
-        ProfScope ps("dense_jumps_scan", st);
-        dense_scan_launch<DD>(G, L, open, st);
-      }
-      {
-        ProfScope ps("dense_jumps_replay", st);
-        hipLaunchKernelGGL(dense_jumps_replay_kernel<DD>, dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s, obs, plane,
-                           L.pre, L.suf, L.bprior, L.bsuffix, L.filt, delta);
-      }
-      rc = jumps_combine(delta, true, 1, plane, it == n_iters - 2 ? change : nullptr, T, K, nu, D, st);
+      dense_tv_prelude<DD>(P, obs, plane, 1, "dense_jumps_summarize", "dense_jumps_scan", st);
+      dense_pass_launch(P, "dense_jumps_replay", st, dense_jumps_replay_kernel<DD>, obs, plane, P.L.pre, P.L.suf,
+                        P.L.bprior, P.L.bsuffix, P.L.filt, delta);
+      rc = jumps_combine(delta, true, 1, plane, it == n_iters - 2 ? change : nullptr, T, K, nu, DD, st);
       if (rc != EKS_OK) return rc;
     }
   })
   return dense_smooth_tv(d, y, var, plane, 1, Mm, ms, Vs, ws, ws_bytes, st);
 }
 
-// ---- eks_em_stats on general models: dense_increments' organisation with the outputs replaced by a sum -----------
-// dense_summarize -> dense_scan -> dense_scan_blocks as they are, then a replay that accumulates the chunk's share of
-// Sw = sum_t E[w_t w_t^T | y] in float64 (eks_em_lane.hpp: dense_em_chunk) into a [chunk][keypoint] plane of D x D
-// (or D, with VS_DIAG) partials behind the generic layout, then eks_em.hip's fixed-order reduce.
+// ---- eks_em_stats: dense_increments' organisation with the outputs replaced by a sum --------------------------------
+// The replay accumulates the chunk's share of Sw = sum_t E[w_t w_t^T | y] in float64 (eks_em_lane.hpp: dense_em_chunk),
+// then eks_em.hip's fixed-order reduce.  Tail: the [chunk][keypoint] plane of D x D (or D, with VS_DIAG) partials.
 template <int D, typename Obs>
 __global__ __launch_bounds__(64) void dense_em_kernel(DenseGeom G, DenseModelPtrs M, const double* __restrict__ s,
                                                      Obs obs, const double* __restrict__ pre,
@@ -736,48 +748,37 @@ __global__ __launch_bounds__(64) void dense_em_kernel(DenseGeom G, DenseModelPtr
                          part + (size_t)idx * w, diag != 0);
 }
 
-static size_t dense_em_part_bytes(int K, int D, int nc) { return align_up((size_t)nc * K * D * D * 8, 256); }
-
+static size_t dense_em_tail_bytes(int T, int K, int D) {
+  return dense_plane_bytes((size_t)dense_nc(T, K) * K * D * D, sizeof(double));
+}
 size_t dense_em_workspace_bytes(int T, int K, int D, int O) {
-  if (D < 1 || D > 6 || O < 1 || O > 64) return 0;
-  const int B = dense_chunk(T, K), nc = (T + B - 1) / B;
-  if ((long long)K * nc >= (1 << 30)) return 0;   // dense_em: EKS_ERR_SHAPE
-  return generic_layout(T, K, D, nc, nullptr).bytes + dense_em_part_bytes(K, D, nc);
+  return dense_generic_workspace_bytes(T, K, D, O, T, dense_em_tail_bytes(T, K, D));
 }
 
 int dense_em_stats(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double* Sw, void* ws,
                    size_t ws_bytes, hipStream_t st) {
-  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
-  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
-  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
-  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
-  if (ws_bytes < dense_em_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
-  const int lanes = K * G.nc;
-  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
-  const GenericLayout L = generic_layout(T, K, D, G.nc, static_cast<char*>(ws));
-  double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + L.bytes);
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim;
+  DensePass P;
+  const int rc = dense_pass_begin(d, Mm, T, dense_em_tail_bytes(T, K, D), ws, ws_bytes, P);
+  if (rc != EKS_OK) return rc;
+  double* part = reinterpret_cast<double*>(P.tail);
   const int diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
-  const Gate open{nullptr, 0.0};
   EKS_DISPATCH_D(D, {
-    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
-    dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_em_summarize", "dense_em_scan", st);
-    {
-      ProfScope ps("dense_em_replay", st);
-      hipLaunchKernelGGL((dense_em_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s,
-                         obs, L.pre, L.suf, L.bprior, L.bsuffix, L.filt, part, diag);
-    }
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, P.G.O, P.M);
+    dense_prelude<DD>(P.G, P.M, P.s, obs, P.L, kGateOpen, "dense_em_summarize", "dense_em_scan", st);
+    dense_pass_launch(P, "dense_em_replay", st, dense_em_kernel<DD, LinearObs<DD>>, obs, P.L.pre, P.L.suf, P.L.bprior,
+                      P.L.bsuffix, P.L.filt, part, diag);
   })
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_status(e);
   // partials [chunk][keypoint][w]: column (k, entry) of the reduce is Sw's own flat index
-  return em_reduce(part, G.nc, K * (diag ? D : D * D), Sw, st);
+  return em_reduce(part, P.G.nc, K * (diag ? D : D * D), Sw, st);
 }
 
-// ---- eks_innovations on general models: dense_em's organisation, forward only ------------------------------------
-// dense_summarize -> dense_scan -> dense_scan_blocks as they are, then a replay that walks every chunk forwards from
-// the belief that entered it (eks_innov_lane.hpp: dense_innov_chunk): innovations, their variances, nis and the
-// frame's log-likelihood stream out, the chunk's log-likelihood goes to a [chunk][keypoint] plane behind the generic
-// layout (which carries no filtered-belief stream here), then eks_em.hip's fixed-order reduce.
+// ---- eks_innovations: dense_em's organisation, forward only ---------------------------------------------------------
+// The replay walks every chunk forwards from the belief that entered it (eks_innov_lane.hpp: dense_innov_chunk):
+// innovations, their variances, nis and the frame's log-likelihood stream out; then eks_em.hip's fixed-order reduce.
+// No filtered-belief stream.  Tail: the chunks' log-likelihoods [chunk][keypoint].
 template <int D, typename Obs>
 __global__ __launch_bounds__(64) void dense_innov_kernel(DenseGeom G, DenseModelPtrs M, const double* __restrict__ s,
                                                         Obs obs, const double* __restrict__ pre,
@@ -797,40 +798,32 @@ __global__ __launch_bounds__(64) void dense_innov_kernel(DenseGeom G, DenseModel
   if (part) part[idx] = ll;
 }
 
+static size_t dense_innov_tail_bytes(int T, int K) {
+  return dense_plane_bytes((size_t)dense_nc(T, K) * K, sizeof(double));
+}
 size_t dense_innovations_workspace_bytes(int T, int K, int D, int O) {
-  if (D < 1 || D > 6 || O < 1 || O > 64) return 0;
-  const int B = dense_chunk(T, K), nc = (T + B - 1) / B;
-  if ((long long)K * nc >= (1 << 30)) return 0;   // dense_innovations: EKS_ERR_SHAPE
-  return generic_layout(0, K, D, nc, nullptr).bytes + align_up((size_t)nc * K * 8, 256);
+  return dense_generic_workspace_bytes(0, K, D, O, T, dense_innov_tail_bytes(T, K));
 }
 
 int dense_innovations(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, float* innov,
                       float* innov_var, float* nis, float* frame_ll, double* loglik, void* ws, size_t ws_bytes,
                       hipStream_t st) {
-  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
-  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
-  const DenseGeom G = dense_geom(T, K, O, dense_chunk(T, K));
-  if ((long long)K * G.nc >= (1 << 30)) return EKS_ERR_SHAPE;   // every launch indexes its threads with an int
-  if (ws_bytes < dense_innovations_workspace_bytes(T, K, D, O)) return EKS_ERR_WORKSPACE;
-  const int lanes = K * G.nc;
-  const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
-  const GenericLayout L = generic_layout(0, K, D, G.nc, static_cast<char*>(ws));
-  double* part = loglik ? reinterpret_cast<double*>(static_cast<char*>(ws) + L.bytes) : nullptr;
+  const int T = d.n_frames, K = d.n_keypoints;
+  DensePass P;
+  const int rc = dense_pass_begin(d, Mm, 0, dense_innov_tail_bytes(T, K), ws, ws_bytes, P);
+  if (rc != EKS_OK) return rc;
+  double* part = loglik ? reinterpret_cast<double*>(P.tail) : nullptr;
   const DenseInnovOut out{innov, innov_var, nis, frame_ll};
-  const Gate open{nullptr, 0.0};
-  EKS_DISPATCH_D(D, {
-    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, O, M);
-    dense_prelude<DD>(G, M, Mm.s, obs, L, open, "dense_innov_summarize", "dense_innov_scan", st);
-    {
-      ProfScope ps("dense_innov_replay", st);
-      hipLaunchKernelGGL((dense_innov_kernel<DD, LinearObs<DD>>), dim3((lanes + 63) / 64), dim3(64), 0, st, G, M, Mm.s,
-                         obs, L.pre, L.bprior, out, part);
-    }
+  EKS_DISPATCH_D(d.state_dim, {
+    const LinearObs<DD> obs = make_linear_obs<DD>(y, var, K, P.G.O, P.M);
+    dense_prelude<DD>(P.G, P.M, P.s, obs, P.L, kGateOpen, "dense_innov_summarize", "dense_innov_scan", st);
+    dense_pass_launch(P, "dense_innov_replay", st, dense_innov_kernel<DD, LinearObs<DD>>, obs, P.L.pre, P.L.bprior, out,
+                      part);
   })
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_status(e);
   if (!loglik) return EKS_OK;
-  return em_reduce(part, G.nc, K, loglik, st);   // partials [chunk][keypoint]
+  return em_reduce(part, P.G.nc, K, loglik, st);   // partials [chunk][keypoint]
 }
 
 // ---- SCORE form: the optimiser's loss and its derivative from the smoother's own kernels ---------------
