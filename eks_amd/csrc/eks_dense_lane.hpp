@@ -61,7 +61,11 @@ EKS_HD Vec<S, D> load_obs_row(const DenseModelPtrs& M, int k, int O, int o) {
 // Per frame the O observations are folded into information form in plain doubles (they do not
 // depend on the parameters) and absorbed as D pseudo-observations (delem_observe_info).  A frame
 // whose variances span more than 8 decades is absorbed observation by observation instead (the
-// information matrix would lose the large-variance rows to rounding).
+// information matrix would lose the large-variance rows to rounding), and so is every frame of a
+// model with fewer observations than states: its information matrix is singular by construction,
+// and the pivots its Cholesky factor should find at zero come out as rounding noise of either sign -
+// a positive one is divided by (D = 6, O = 1: the loss of one keypoint in three off in the first
+// digit).  O rank-1 updates are also fewer than D there.
 struct ObsNoise {
   const float* var;       // [T][K][O] time-varying ensemble variances, or
   const double* rconst;   // [K][O] constant variances (exactly one of the two is non-null)
@@ -109,7 +113,7 @@ EKS_HD DElem<S, D> loss_summarize_chunk(const float* __restrict__ y, const ObsNo
         for (int j = 0; j < D; ++j) Lam.a[i][j] += h.a[i] * (w * h.a[j]);
       }
     }
-    if (rmax <= 1e8 * rmin) {
+    if (O >= D && rmax <= 1e8 * rmin) {   // (O < D: Lambda has rank O at most, see above)
       delem_observe_info(e, Lam, nu, c);
     } else {
       for (int o = 0; o < O; ++o)

@@ -68,10 +68,16 @@ static inline long dw_units(int T, int K, int B) {
 }
 // (O > 8 - five and six cameras - keeps 8 frames: only that form is instantiated for them.  EKS_DW_CHUNK = 2 / 4 / 8
 // forces a choice for A/B runs; O = 0 asks for the choice that needs the largest workspace.)
+// The short chunks exist for one wave pair per workgroup only (dense_wave_run), so a forced 2 or 4 holds while its units
+// fit that form (kDwUnitsPair); beyond it the call takes 8 frames, and its geometry and workspace with it.  (Until the
+// forms were tested one by one, the geometry kept the forced length under the 8-frame kernels: lanes past the last
+// frame, each storing frame T - 1 beside the lane that owns it.)
+constexpr int kDwUnitsPair = 256;
 static inline int dw_chunk_frames(int T, int K, int O) {
   if (O > 8) return kDwBMax;
   const int forced = knob_int(KNOB_DW_CHUNK, 0);
-  if (forced == 2 || forced == 4 || forced == 8) return forced;
+  if (forced == 8 || ((forced == 2 || forced == 4) && dw_units(T, K, forced) <= kDwUnitsPair)) return forced;
+  if (forced == 2 || forced == 4) return kDwBMax;
   if (dw_units(T, K, 2) <= kDwUnitsShort) return 2;
   if (dw_units(T, K, 4) <= kDwUnitsShort) return 4;
   return kDwBMax;
@@ -769,7 +775,7 @@ static int dense_wave_run(const eks_dims_t& d, int mode, const float* y, const f
   const DenseModelPtrs M{Mm.m0, Mm.S0, Mm.A, Mm.C, Mm.Q};
   const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
   const int units = K * G.nwb;
-  const bool two = units > 256 && O <= 8;             // more (keypoint, 64-chunk) units than CUs: 4-wave workgroups
+  const bool two = units > kDwUnitsPair && O <= 8;    // more (keypoint, 64-chunk) units than CUs: 4-wave workgroups
   const dim3 grid((unsigned)(two ? (units + 1) / 2 : units)), block(two ? 256 : 128);
 #define EKS_DW_SB(DD, OO, SS, MD, BB)                                                                    \
   {                                                                                                      \

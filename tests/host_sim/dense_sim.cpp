@@ -116,10 +116,13 @@ extern "C" int sim_dense_smooth(int T, int K, int D, int O, int B, const float* 
                                 const double* m0, const double* S0, const double* A, const double* C,
                                 const double* Q, const double* s, float* ms, float* Vs) {
   const DenseModelPtrs M{m0, S0, A, C, Q};
-  switch (D) {
+  switch (D) {   // every state dimension the library accepts (EKS_DISPATCH_D)
+    case 1: dense_smooth_sim<1>(T, K, O, B, y, var, M, s, ms, Vs); return 0;
     case 2: dense_smooth_sim<2>(T, K, O, B, y, var, M, s, ms, Vs); return 0;
     case 3: dense_smooth_sim<3>(T, K, O, B, y, var, M, s, ms, Vs); return 0;
     case 4: dense_smooth_sim<4>(T, K, O, B, y, var, M, s, ms, Vs); return 0;
+    case 5: dense_smooth_sim<5>(T, K, O, B, y, var, M, s, ms, Vs); return 0;
+    case 6: dense_smooth_sim<6>(T, K, O, B, y, var, M, s, ms, Vs); return 0;
     default: return -3;
   }
 }
@@ -166,9 +169,12 @@ extern "C" int sim_dense_nll(int T, int K, int D, int O, int B, const float* y, 
   for (int k = 0; k < K; ++k) {
     DualD ll;
     switch (D) {
+      case 1: ll = scaled_ll<DualD, 1>(T, K, O, B, k, y, rconst, M, s[k]); break;
       case 2: ll = scaled_ll<DualD, 2>(T, K, O, B, k, y, rconst, M, s[k]); break;
       case 3: ll = scaled_ll<DualD, 3>(T, K, O, B, k, y, rconst, M, s[k]); break;
       case 4: ll = scaled_ll<DualD, 4>(T, K, O, B, k, y, rconst, M, s[k]); break;
+      case 5: ll = scaled_ll<DualD, 5>(T, K, O, B, k, y, rconst, M, s[k]); break;
+      case 6: ll = scaled_ll<DualD, 6>(T, K, O, B, k, y, rconst, M, s[k]); break;
       default: return -3;
     }
     nll[k] = -ll.v;

@@ -46,8 +46,9 @@ def test_scalar_reference_against_the_joint_posterior(a, c, s):
     assert worst < 1e-11
 
 
-@pytest.mark.parametrize('singular_q', [False, True])
-@pytest.mark.parametrize('D,O', [(3, 4), (5, 6)])
+@pytest.mark.parametrize('D,O,singular_q', [(3, 4, False), (5, 6, False), (3, 4, True), (5, 6, True),
+                                           # the pairs the GPU test adds at the accepted width (tests/dense_forms.py)
+                                           (1, 64, False), (6, 33, False), (3, 5, False)])
 def test_dense_reference_against_the_joint_posterior(D, O, singular_q):
     T, K = 12, 2
     M = dense_case(K, D, O, singular_q, seed=D)

@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import em_ref  # noqa: E402
 from test_increments_cpu import dense_case, make_session  # noqa: E402
 from test_gpu_increments import PARAMS, _dev, dense_session, diag_flags, edge_session, stable  # noqa: E402
+from dense_forms import general_grid, general_seed  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -146,10 +147,10 @@ def check_dense(label, M, y, var, got, vs_diag):
     return err
 
 
-@pytest.mark.parametrize('K', [1, 3, 65])
-@pytest.mark.parametrize('D,O', [(1, 1), (3, 4), (6, 12)])
+# (and the accepted width, odd O past 32 and the smallest odd O, at K = 3: tests/dense_forms.py WIDE_PAIRS)
+@pytest.mark.parametrize('D,O,K', general_grid([(1, 1), (3, 4), (6, 12)]))
 def test_general_models_against_the_dense_reference(D, O, K, set_knob):
-    M = stable(dense_case(K, D, O, False, seed=10 * D + K))
+    M = stable(dense_case(K, D, O, False, seed=general_seed(D, O, K)))
     worst = 0.0
     for i, T in enumerate((1, 2, 15, 16, 17, 33, 100)):
         y, var = dense_session(M, T, O, seed=T)

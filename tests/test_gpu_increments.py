@@ -35,6 +35,7 @@ import increments_ref as iref  # noqa: E402
 import sampling_ref as sref  # noqa: E402
 from test_increments_cpu import (NAMES, dense_case, entry_error, make_session, moment_errors, references,  # noqa: E402
                                  rule_excess, scaled_error)
+from dense_forms import general_grid, general_seed  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -249,10 +250,10 @@ def check_dense(label, M, y, var, got, vs_diag):
     return ', '.join(figs), r64
 
 
-@pytest.mark.parametrize('K', [1, 3, 65])
-@pytest.mark.parametrize('D,O', [(1, 1), (2, 2), (3, 4), (6, 12)])
+# (and the accepted width, odd O past 32 and the smallest odd O, at K = 3: tests/dense_forms.py WIDE_PAIRS)
+@pytest.mark.parametrize('D,O,K', general_grid([(1, 1), (2, 2), (3, 4), (6, 12)]))
 def test_general_models_against_the_dense_reference(D, O, K, set_knob):
-    M = stable(dense_case(K, D, O, False, seed=10 * D + K))
+    M = stable(dense_case(K, D, O, False, seed=general_seed(D, O, K)))
     figs = ''
     for i, T in enumerate((1, 2, 15, 16, 17, 33, 100)):
         y, var = dense_session(M, T, O, seed=T)

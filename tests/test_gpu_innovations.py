@@ -33,6 +33,7 @@ import innovations_ref as iref  # noqa: E402
 from test_increments_cpu import dense_case, make_session  # noqa: E402
 from test_gpu_increments import PARAMS, _dev, dense_session, diag_flags, edge_session, stable  # noqa: E402
 from test_gpu_em import make_loop, subset  # noqa: E402
+from dense_forms import general_grid, general_seed  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -156,10 +157,10 @@ def check_dense(label, M, y, var, got, worst=None):
     return ', '.join(figs)
 
 
-@pytest.mark.parametrize('K', [1, 3, 65])
-@pytest.mark.parametrize('D,O', [(1, 1), (2, 3), (3, 4), (6, 12)])
+# (and the accepted width, odd O past 32 and the smallest odd O, at K = 3: tests/dense_forms.py WIDE_PAIRS)
+@pytest.mark.parametrize('D,O,K', general_grid([(1, 1), (2, 3), (3, 4), (6, 12)]))
 def test_general_models_against_the_two_float64_forms(D, O, K, set_knob):
-    M = stable(dense_case(K, D, O, False, seed=10 * D + K))
+    M = stable(dense_case(K, D, O, False, seed=general_seed(D, O, K)))
     worst = {}
     for T in (1, 2, 16, 17, 33, 100):
         y, var = dense_session(M, T, O, seed=T)

@@ -32,6 +32,7 @@ import smooth_tv_ref as tref  # noqa: E402
 from test_increments_cpu import dense_case, make_session  # noqa: E402
 from test_gpu_increments import PARAMS, _dev, dense_session, diag_flags, stable  # noqa: E402
 from test_gpu_em import subset  # noqa: E402
+from dense_forms import general_grid, general_seed  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -466,10 +467,10 @@ def check_dense(label, got, seq, joint, worst=None):
         assert excess <= 1.0, f'{label}: {name} is {excess:.3g} x its bar {bar:.3g} (+ one float32 ulp)'
 
 
-@pytest.mark.parametrize('K', [1, 3, 65])
-@pytest.mark.parametrize('D,O', [(1, 1), (2, 3), (3, 4), (6, 12)])
+# (and the accepted width, odd O past 32 and the smallest odd O, at K = 3: tests/dense_forms.py WIDE_PAIRS)
+@pytest.mark.parametrize('D,O,K', general_grid([(1, 1), (2, 3), (3, 4), (6, 12)]))
 def test_general_models_against_the_two_float64_forms(D, O, K, set_knob):
-    M = stable(dense_case(K, D, O, False, seed=10 * D + K))
+    M = stable(dense_case(K, D, O, False, seed=general_seed(D, O, K)))
     worst = {}
     for i, T in enumerate((1, 2, 17, 33, 100)):
         y, var = dense_jumpy(M, T, O, seed=T)

@@ -1,10 +1,16 @@
 """GPU parity tests: every entry point of libeks_hip.so against the float64 CPU oracle on seeded
 inputs small enough for the oracle to finish in seconds.  Tolerances (stated per test) derive from
 BASELINE.json's bar: smoothed means / covariances within 1e-5 relative, indices bit-exact."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from oracle import eks_oracle as orc
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from dense_forms import dense_problem as _dense_problem, rel as _rel  # noqa: E402  (shared with tests/test_gpu_dense_forms.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,12 +40,6 @@ def _singlecam_problem(T, K, seed, unit=True):
     arrs['ys'] = np.transpose(y_tk, (1, 0, 2)).astype(np.float64)          # oracle sees f32 inputs
     arrs['ensemble_vars'] = var_tk.astype(np.float64)
     return arrs, y_tk, var_tk
-
-
-def _rel(a, b, axis_scale=None):
-    """max |a-b| relative to the per-keypoint max magnitude of b (BASELINE's 'relative', H4)."""
-    sc = np.abs(b).max(axis=axis_scale, keepdims=True) if axis_scale is not None else np.abs(b).max()
-    return float((np.abs(a - b) / np.maximum(sc, 1e-300)).max())
 
 
 def _params_dev(arrs):
@@ -247,23 +247,6 @@ def test_smooth_diag_with_variances_at_the_clip(sval):
     assert _rel(ms, ms_o, axis_scale=(1, 2)) < 1e-5
     Vd_o = np.diagonal(Vs_o, axis1=2, axis2=3)
     assert (np.abs(Vs - Vd_o) / Vd_o).max() < 1e-5
-
-
-def _dense_problem(T, K, D, O, seed):
-    rng = np.random.default_rng(seed)
-    x = np.cumsum(rng.standard_normal((K, T, D)) * 0.5, axis=1)
-    C = rng.standard_normal((K, O, D))
-    var = (rng.gamma(2.0, 0.4, (T, K, O)) + 0.02).astype(np.float32)
-    y = np.einsum('kod,ktd->tko', C, x) + rng.standard_normal((T, K, O)) * np.sqrt(var)
-    y = y.astype(np.float32)
-    L = rng.standard_normal((K, D, D)) * 0.3
-    Q = L @ np.swapaxes(L, 1, 2) + 0.2 * np.eye(D)
-    Q = Q / np.abs(Q).max(axis=(1, 2), keepdims=True)
-    S0 = np.eye(D) * rng.uniform(1.0, 5.0, (K, D))[:, :, None]
-    A = np.tile(np.eye(D), (K, 1, 1))
-    m0 = np.zeros((K, D))
-    return dict(ys=np.transpose(y, (1, 0, 2)).astype(np.float64), m0s=m0, S0s=S0, As=A, Cs=C, Qs=Q,
-                ensemble_vars=var.astype(np.float64)), y, var
 
 
 @pytest.mark.parametrize('T,K,D,O,general_A', [

@@ -211,6 +211,7 @@ def test_parity_at_size_runs_32_frame_chunks(unit_root):
     (4, 8, 2, 2, 'generic B=16'),        # D = 4
     (5, 6, 3, 2, 'generic B=16'),        # D = 5
     (6, 12, 3, 3, 'generic B=16'),       # D = 6
+    (2, 64, 3, 2, 'generic B=16'),       # the widest observation the library accepts
     (2, 2, 3, 3, 'wave B=2'),            # Kp = 12: 12 ceil(550 / 64) = 108 <= 160 units -> wave, 2-frame chunks, 9 blocks
     (2, 2, 5, 5, 'wave B=4'),            # Kp = 30: 30 x 9 = 270 > 160, 30 ceil(275 / 64) = 150 <= 160 -> 4-frame chunks
     (3, 10, 3, 3, 'wave B=8'),           # O > 8 keeps 8 frames: 138 chunks, 12 x 3 = 36 units -> wave (five-camera form)

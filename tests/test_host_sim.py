@@ -335,8 +335,8 @@ def test_dense_chunked_smoother_matches_oracle_also_at_the_variance_clip(dense_s
         var[::5] = 1e-8
     elif case == 'one_clipped':
         var[::7, :, 1] = 0.0
-    y = (np.einsum('kod,ktd->tko', C, x) + rng.standard_normal((T, K, O)) * np.sqrt(np.maximum(var, 1e-12))
-         ).astype(np.float32)
+    y = np.ascontiguousarray((np.einsum('kod,ktd->tko', C, x)
+                              + rng.standard_normal((T, K, O)) * np.sqrt(np.maximum(var, 1e-12))).astype(np.float32))
     L = rng.standard_normal((K, D, D)) * 0.3
     Q = L @ np.swapaxes(L, 1, 2) + 0.2 * np.eye(D)
     m0, S0, A = np.zeros((K, D)), np.tile(4 * np.eye(D), (K, 1, 1)), np.tile(np.eye(D), (K, 1, 1))
@@ -358,7 +358,39 @@ def test_dense_chunked_smoother_matches_oracle_also_at_the_variance_clip(dense_s
     assert (np.abs(Vs_k - Vs_o) / np.abs(Vs_o).max(axis=1, keepdims=True)).max() < 1e-6
 
 
-@pytest.mark.parametrize('D,O,general_A', [(3, 4, False), (2, 2, True), (4, 8, False)])
+@pytest.mark.parametrize('D,O', [(6, 64), (1, 1)])
+def test_dense_chunked_smoother_at_the_accepted_limits_matches_oracle(dense_sim, D, O):
+    """The lane bodies of eks_dense_lane.hpp at the widest and the narrowest model the library accepts (D = 6 with
+    O = 64, D = O = 1), at the bars of the test above; T = 70 in 16-frame chunks: a ragged last chunk of 6."""
+    rng = np.random.default_rng(100 * D + O)
+    T, K, B = 70, 3, 16
+    x = np.cumsum(rng.standard_normal((K, T, D)) * 0.7, axis=1)
+    C = np.ascontiguousarray(np.linalg.qr(rng.standard_normal((K, O, D)))[0])
+    var = (0.25 * rng.gamma(2.0, 1.0, (T, K, O))).clip(1e-3).astype(np.float32)
+    y = np.ascontiguousarray((np.einsum('kod,ktd->tko', C, x) + rng.standard_normal((T, K, O)) * np.sqrt(var)
+                              ).astype(np.float32))
+    L = rng.standard_normal((K, D, D)) * 0.3
+    Q = L @ np.swapaxes(L, 1, 2) + 0.2 * np.eye(D)
+    m0, S0 = np.zeros((K, D)), np.tile(4 * np.eye(D), (K, 1, 1))
+    A = np.tile(np.eye(D), (K, 1, 1)) * 0.97 + 0.02 * rng.standard_normal((K, D, D))
+    s = np.exp(rng.uniform(-3, 3, K))
+    ms = np.zeros((T, K, D), np.float32)
+    Vs = np.zeros((T, K, D, D), np.float32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+    assert dense_sim.sim_dense_smooth(T, K, D, O, B, p(y), p(var), p(m0), p(S0), p(A), p(C), p(Q), p(s),
+                                      p(ms), p(Vs)) == 0
+    ys = np.swapaxes(y, 0, 1).astype(np.float64)
+    Rd = np.maximum(np.swapaxes(var.astype(np.float64), 0, 1), 1e-12)
+    ms_o, Vs_o = orc.kalman_smoother(ys, m0, S0, A, C, Q, s, Rd)[:2]
+    ms_k, Vs_k = np.swapaxes(ms, 0, 1), np.swapaxes(Vs, 0, 1)
+    assert (np.abs(ms_k - ms_o) / np.abs(ms_o).max(axis=(1, 2), keepdims=True)).max() < 1e-6
+    assert (np.abs(Vs_k - Vs_o) / np.abs(Vs_o).max(axis=1, keepdims=True)).max() < 1e-6
+
+
+@pytest.mark.parametrize('D,O,general_A', [(3, 4, False), (2, 2, True), (4, 8, False),
+                                          # the accepted limits of the general path (D <= 6, O <= 64), odd O past 32
+                                          (1, 1, False), (1, 33, True), (1, 64, False), (5, 1, True), (5, 33, False),
+                                          (5, 64, True), (6, 1, False), (6, 33, True), (6, 64, False)])
 def test_dense_loss_and_log_s_sensitivity_match_oracle(dense_sim, D, O, general_A):
     """eks_nll on the general path: predict-first chunk elements, D pseudo-observations per frame,
     tree composition, dual-number d/dlog s - against the oracle's filter and forward sensitivity."""
@@ -366,7 +398,8 @@ def test_dense_loss_and_log_s_sensitivity_match_oracle(dense_sim, D, O, general_
     T, K, B = 900, 3, 8
     x = np.cumsum(rng.standard_normal((K, T, D)) * 0.5, axis=1)
     C = rng.standard_normal((K, O, D))
-    y = (np.einsum('kod,ktd->tko', C, x) + rng.standard_normal((T, K, O)) * 0.7).astype(np.float32)
+    # (contiguous: einsum chooses its output's strides, and astype keeps them - the simulator takes a plain pointer)
+    y = np.ascontiguousarray((np.einsum('kod,ktd->tko', C, x) + rng.standard_normal((T, K, O)) * 0.7).astype(np.float32))
     L = rng.standard_normal((K, D, D)) * 0.3
     Q = L @ np.swapaxes(L, 1, 2) + 0.2 * np.eye(D)
     A = np.tile(np.eye(D), (K, 1, 1))
