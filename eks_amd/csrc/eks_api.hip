@@ -20,6 +20,69 @@ static int check_dims(const eks_dims_t* d) {
   return EKS_OK;
 }
 
+// The model-taking entries (eks_smooth, _tv, _robust, _jumps, _increments, eks_em_stats, eks_innovations, eks_sample,
+// eks_nll, eks_nll_argmin) share one tail, stated once here.  Each entry keeps its own shape check in front of it; the
+// ORDER of an entry's checks is part of its contract (tests/test_api_refusals_cpu.py pins every status).
+
+// the caller's eight model pointers; r is var, or rconst on the NLL entries (where s is the candidates)
+struct ModelArgs {
+  const float* y;
+  const void* r;
+  const double *m0, *S0, *A, *C, *Q, *s;
+};
+
+// EKS_ERR_WORKSPACE for no workspace or one below `need` (0: the size is diag_X / dense_X's own to test)
+static int workspace_status(const void* workspace, size_t workspace_bytes, size_t need = 0) {
+  return !workspace || workspace_bytes < need ? EKS_ERR_WORKSPACE : EKS_OK;
+}
+
+// The eight-pointer null test, then `rest` - the status of the entry's LATER checks (its other pointers, the workspace,
+// the size), which are host arithmetic and so may be evaluated by the caller up front - then the dispatch: scalar
+// chains (EKS_FLAG_DIAG_MODEL) get a DiagModel in `diag`, general models a DenseModel in `dense`.  d has been checked.
+template <class Diag, class Dense>
+static int model_call(const eks_dims_t* d, const ModelArgs& a, int rest, Diag diag, Dense dense) {
+  if (!a.y || !a.r || !a.m0 || !a.S0 || !a.A || !a.C || !a.Q || !a.s) return EKS_ERR_NULL;
+  if (rest != EKS_OK) return rest;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag(DiagModel{a.m0, a.S0, a.A, a.C, a.Q, a.s, d->state_dim});
+  return dense(DenseModel{a.m0, a.S0, a.A, a.C, a.Q, a.s});
+}
+
+// A workspace query: 0 where the entry's shape check (`status`) refuses, else diag(T, N) or dense(T, K, D, O).
+template <class Diag, class Dense>
+static size_t model_bytes(const eks_dims_t* d, int status, Diag diag, Dense dense) {
+  if (status != EKS_OK) return 0;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag(d->n_frames, d->n_keypoints * d->state_dim);
+  return dense(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+}
+
+// shapes eks_smooth_tv takes (EKS_OK) or the status it refuses them with; nothing here touches the device
+static int smooth_tv_check(const eks_dims_t* d) {
+  const int rc = check_dims(d);
+  if (rc != EKS_OK) return rc;
+  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_smooth_tv_check(*d);
+  if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
+  return dense_smooth_tv_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim) ? EKS_OK : EKS_ERR_SHAPE;
+}
+
+// eks_smooth_robust and eks_smooth_jumps: one entry around two pairs of kernels whose signatures agree; `plane` is the
+// weights of the one and the scales of the other, `need` the entry's workspace query.  Order: eks_smooth_tv's shapes and
+// refusals, nu / n_iters, the model's pointers, the outputs and a plane that is to be read, the workspace, its size.
+template <class Diag, class Dense>
+static int smooth_iterated(const eks_dims_t* d, const ModelArgs& a, double nu, int32_t n_iters, float* plane,
+                           int32_t plane_in, float* change, float* ms, float* Vs, void* workspace, size_t workspace_bytes,
+                           eks_stream_t stream, size_t need(const eks_dims_t*), Diag diag, Dense dense) {
+  const int rc = smooth_tv_check(d);
+  if (rc != EKS_OK) return rc;
+  if (!(nu > 0.0) || !(nu <= 1.7e308) || n_iters < 1) return EKS_ERR_SHAPE;
+  auto run = [&](auto kernels, const auto& M) {
+    return kernels(*d, a.y, static_cast<const float*>(a.r), M, nu, n_iters, plane, plane_in, change, ms, Vs, workspace,
+                   workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  };
+  return model_call(
+      d, a, !ms || !Vs || (plane_in && !plane) ? EKS_ERR_NULL : workspace_status(workspace, workspace_bytes, need(d)),
+      [&](const DiagModel& M) { return run(diag, M); }, [&](const DenseModel& M) { return run(dense, M); });
+}
+
 extern "C" {
 
 const char* eks_version(void) { return "eks_hip 0.1 (gfx950)"; }
@@ -39,10 +102,7 @@ const char* eks_status_string(int status) {
 }
 
 size_t eks_smooth_workspace_bytes(const eks_dims_t* d) {
-  if (check_dims(d) != EKS_OK) return 0;
-  if (d->flags & EKS_FLAG_DIAG_MODEL)
-    return diag_smooth_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
-  return dense_smooth_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+  return model_bytes(d, check_dims(d), diag_smooth_workspace_bytes, dense_smooth_workspace_bytes);
 }
 
 int eks_smooth(const eks_dims_t* d, const float* y, const float* var, const double* m0,
@@ -51,30 +111,15 @@ int eks_smooth(const eks_dims_t* d, const float* y, const float* var, const doub
                eks_stream_t stream) {
   const int rc = check_dims(d);
   if (rc != EKS_OK) return rc;
-  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s || !ms || !Vs) return EKS_ERR_NULL;
-  if (!workspace) return EKS_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
-    return diag_smooth(*d, y, var, M, ms, Vs, workspace, workspace_bytes, st);
-  }
-  const DenseModel M{m0, S0, A, C, Q, s};
-  return dense_smooth(*d, y, var, M, ms, Vs, workspace, workspace_bytes, st);
-}
-
-// shapes eks_smooth_tv takes (EKS_OK) or the status it refuses them with; nothing here touches the device
-static int smooth_tv_check(const eks_dims_t* d) {
-  const int rc = check_dims(d);
-  if (rc != EKS_OK) return rc;
-  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_smooth_tv_check(*d);
-  if (d->state_dim > 6 || d->obs_dim > 64) return EKS_ERR_UNSUPPORTED;
-  return dense_smooth_tv_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim) ? EKS_OK : EKS_ERR_SHAPE;
+  return model_call(
+      d, {y, var, m0, S0, A, C, Q, s}, !ms || !Vs ? EKS_ERR_NULL : workspace_status(workspace, workspace_bytes),
+      [&](const DiagModel& M) { return diag_smooth(*d, y, var, M, ms, Vs, workspace, workspace_bytes, st); },
+      [&](const DenseModel& M) { return dense_smooth(*d, y, var, M, ms, Vs, workspace, workspace_bytes, st); });
 }
 
 size_t eks_smooth_tv_workspace_bytes(const eks_dims_t* d) {
-  if (smooth_tv_check(d) != EKS_OK) return 0;
-  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_em_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
-  return dense_smooth_tv_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+  return model_bytes(d, smooth_tv_check(d), diag_em_workspace_bytes, dense_smooth_tv_workspace_bytes);
 }
 
 int eks_smooth_tv(const eks_dims_t* d, const float* y, const float* var, const float* qscale,
@@ -83,72 +128,45 @@ int eks_smooth_tv(const eks_dims_t* d, const float* y, const float* var, const f
                   eks_stream_t stream) {
   const int rc = smooth_tv_check(d);
   if (rc != EKS_OK) return rc;
-  if (!y || !var || !qscale || !m0 || !S0 || !A || !C || !Q || !s || !ms || !Vs) return EKS_ERR_NULL;
-  if (!workspace) return EKS_ERR_WORKSPACE;
-  if (workspace_bytes < eks_smooth_tv_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
-    return diag_smooth_tv(*d, y, var, qscale, qscale_per_keypoint, M, ms, Vs, workspace, workspace_bytes, st);
-  }
-  const DenseModel M{m0, S0, A, C, Q, s};
-  return dense_smooth_tv(*d, y, var, qscale, qscale_per_keypoint, M, ms, Vs, workspace, workspace_bytes, st);
+  return model_call(
+      d, {y, var, m0, S0, A, C, Q, s},
+      !qscale || !ms || !Vs ? EKS_ERR_NULL
+                            : workspace_status(workspace, workspace_bytes, eks_smooth_tv_workspace_bytes(d)),
+      [&](const DiagModel& M) {
+        return diag_smooth_tv(*d, y, var, qscale, qscale_per_keypoint, M, ms, Vs, workspace, workspace_bytes, st);
+      },
+      [&](const DenseModel& M) {
+        return dense_smooth_tv(*d, y, var, qscale, qscale_per_keypoint, M, ms, Vs, workspace, workspace_bytes, st);
+      });
 }
 
 size_t eks_smooth_robust_workspace_bytes(const eks_dims_t* d) {
-  if (smooth_tv_check(d) != EKS_OK) return 0;
-  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_smooth_robust_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
-  return dense_smooth_robust_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+  return model_bytes(d, smooth_tv_check(d), diag_smooth_robust_workspace_bytes, dense_smooth_robust_workspace_bytes);
+}
+
+size_t eks_smooth_jumps_workspace_bytes(const eks_dims_t* d) {
+  return model_bytes(
+      d, smooth_tv_check(d), [d](int T, int) { return diag_smooth_jumps_workspace_bytes(T, d->n_keypoints, d->state_dim); },
+      dense_smooth_jumps_workspace_bytes);
 }
 
 int eks_smooth_robust(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
                       const double* A, const double* C, const double* Q, const double* s, double nu, int32_t n_iters,
                       float* weights, int32_t weights_in, float* change, float* ms, float* Vs, void* workspace,
                       size_t workspace_bytes, eks_stream_t stream) {
-  const int rc = smooth_tv_check(d);   // eks_smooth_tv's shapes and refusals
-  if (rc != EKS_OK) return rc;
-  if (!(nu > 0.0) || !(nu <= 1.7e308) || n_iters < 1) return EKS_ERR_SHAPE;
-  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s || !ms || !Vs) return EKS_ERR_NULL;
-  if (weights_in && !weights) return EKS_ERR_NULL;
-  if (!workspace) return EKS_ERR_WORKSPACE;
-  if (workspace_bytes < eks_smooth_robust_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
-    return diag_smooth_robust(*d, y, var, M, nu, n_iters, weights, weights_in, change, ms, Vs, workspace,
-                              workspace_bytes, st);
-  }
-  const DenseModel M{m0, S0, A, C, Q, s};
-  return dense_smooth_robust(*d, y, var, M, nu, n_iters, weights, weights_in, change, ms, Vs, workspace,
-                             workspace_bytes, st);
-}
-
-size_t eks_smooth_jumps_workspace_bytes(const eks_dims_t* d) {
-  if (smooth_tv_check(d) != EKS_OK) return 0;
-  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_smooth_jumps_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim);
-  return dense_smooth_jumps_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+  return smooth_iterated(d, {y, var, m0, S0, A, C, Q, s}, nu, n_iters, weights, weights_in, change, ms, Vs, workspace,
+                         workspace_bytes, stream, eks_smooth_robust_workspace_bytes, diag_smooth_robust,
+                         dense_smooth_robust);
 }
 
 int eks_smooth_jumps(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
                      const double* A, const double* C, const double* Q, const double* s, double nu, int32_t n_iters,
                      float* scales, int32_t scales_in, float* change, float* ms, float* Vs, void* workspace,
                      size_t workspace_bytes, eks_stream_t stream) {
-  const int rc = smooth_tv_check(d);   // eks_smooth_tv's shapes and refusals
-  if (rc != EKS_OK) return rc;
-  if (!(nu > 0.0) || !(nu <= 1.7e308) || n_iters < 1) return EKS_ERR_SHAPE;
-  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s || !ms || !Vs) return EKS_ERR_NULL;
-  if (scales_in && !scales) return EKS_ERR_NULL;
-  if (!workspace) return EKS_ERR_WORKSPACE;
-  if (workspace_bytes < eks_smooth_jumps_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
-    return diag_smooth_jumps(*d, y, var, M, nu, n_iters, scales, scales_in, change, ms, Vs, workspace, workspace_bytes,
-                             st);
-  }
-  const DenseModel M{m0, S0, A, C, Q, s};
-  return dense_smooth_jumps(*d, y, var, M, nu, n_iters, scales, scales_in, change, ms, Vs, workspace, workspace_bytes,
-                            st);
+  return smooth_iterated(d, {y, var, m0, S0, A, C, Q, s}, nu, n_iters, scales, scales_in, change, ms, Vs, workspace,
+                         workspace_bytes, stream, eks_smooth_jumps_workspace_bytes, diag_smooth_jumps,
+                         dense_smooth_jumps);
 }
 
 // shapes eks_smooth_increments takes (EKS_OK) or the status it refuses them with; nothing here touches the device
@@ -164,10 +182,7 @@ static int increments_check(const eks_dims_t* d) {
 }
 
 size_t eks_smooth_increments_workspace_bytes(const eks_dims_t* d) {
-  if (increments_check(d) != EKS_OK) return 0;
-  if (d->flags & EKS_FLAG_DIAG_MODEL)
-    return diag_increments_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
-  return dense_increments_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+  return model_bytes(d, increments_check(d), diag_increments_workspace_bytes, dense_increments_workspace_bytes);
 }
 
 int eks_smooth_increments(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
@@ -176,16 +191,16 @@ int eks_smooth_increments(const eks_dims_t* d, const float* y, const float* var,
                           eks_stream_t stream) {
   const int rc = increments_check(d);
   if (rc != EKS_OK) return rc;
-  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s) return EKS_ERR_NULL;
-  if (!lag1 && !dmean && !dV) return EKS_ERR_NULL;
-  if (!workspace) return EKS_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
-    return diag_increments(*d, y, var, M, ms, Vs, lag1, dmean, dV, workspace, workspace_bytes, st);
-  }
-  const DenseModel M{m0, S0, A, C, Q, s};
-  return dense_increments(*d, y, var, M, ms, Vs, lag1, dmean, dV, workspace, workspace_bytes, st);
+  return model_call(
+      d, {y, var, m0, S0, A, C, Q, s},
+      !lag1 && !dmean && !dV ? EKS_ERR_NULL : workspace_status(workspace, workspace_bytes),
+      [&](const DiagModel& M) {
+        return diag_increments(*d, y, var, M, ms, Vs, lag1, dmean, dV, workspace, workspace_bytes, st);
+      },
+      [&](const DenseModel& M) {
+        return dense_increments(*d, y, var, M, ms, Vs, lag1, dmean, dV, workspace, workspace_bytes, st);
+      });
 }
 
 // shapes eks_em_stats takes (EKS_OK) or the status it refuses them with; nothing here touches the device
@@ -202,9 +217,7 @@ static int em_check(const eks_dims_t* d) {
 }
 
 size_t eks_em_stats_workspace_bytes(const eks_dims_t* d) {
-  if (em_check(d) != EKS_OK) return 0;
-  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_em_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
-  return dense_em_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+  return model_bytes(d, em_check(d), diag_em_workspace_bytes, dense_em_workspace_bytes);
 }
 
 int eks_em_stats(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
@@ -212,16 +225,12 @@ int eks_em_stats(const eks_dims_t* d, const float* y, const float* var, const do
                  size_t workspace_bytes, eks_stream_t stream) {
   const int rc = em_check(d);
   if (rc != EKS_OK) return rc;
-  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s || !Sw) return EKS_ERR_NULL;
-  if (!workspace) return EKS_ERR_WORKSPACE;
-  if (workspace_bytes < eks_em_stats_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
-    return diag_em_stats(*d, y, var, M, Sw, workspace, workspace_bytes, st);
-  }
-  const DenseModel M{m0, S0, A, C, Q, s};
-  return dense_em_stats(*d, y, var, M, Sw, workspace, workspace_bytes, st);
+  return model_call(
+      d, {y, var, m0, S0, A, C, Q, s},
+      !Sw ? EKS_ERR_NULL : workspace_status(workspace, workspace_bytes, eks_em_stats_workspace_bytes(d)),
+      [&](const DiagModel& M) { return diag_em_stats(*d, y, var, M, Sw, workspace, workspace_bytes, st); },
+      [&](const DenseModel& M) { return dense_em_stats(*d, y, var, M, Sw, workspace, workspace_bytes, st); });
 }
 
 // shapes eks_innovations takes (EKS_OK) or the status it refuses them with; nothing here touches the device.
@@ -237,9 +246,7 @@ static int innovations_check(const eks_dims_t* d) {
 }
 
 size_t eks_innovations_workspace_bytes(const eks_dims_t* d) {
-  if (innovations_check(d) != EKS_OK) return 0;
-  if (d->flags & EKS_FLAG_DIAG_MODEL) return diag_em_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim);
-  return dense_innovations_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim);
+  return model_bytes(d, innovations_check(d), diag_em_workspace_bytes, dense_innovations_workspace_bytes);
 }
 
 int eks_innovations(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
@@ -248,19 +255,19 @@ int eks_innovations(const eks_dims_t* d, const float* y, const float* var, const
                     size_t workspace_bytes, eks_stream_t stream) {
   const int rc = innovations_check(d);
   if (rc != EKS_OK) return rc;
-  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s) return EKS_ERR_NULL;
-  if (!innov && !innov_var && !nis && !frame_ll && !loglik) return EKS_ERR_NULL;
+  int rest = workspace_status(workspace, workspace_bytes, eks_innovations_workspace_bytes(d));
+  if (!innov && !innov_var && !nis && !frame_ll && !loglik) rest = EKS_ERR_NULL;
   // scalar chains: nis and frame_ll are elementwise functions of innov and innov_var
-  if ((d->flags & EKS_FLAG_DIAG_MODEL) && (nis || frame_ll)) return EKS_ERR_UNSUPPORTED;
-  if (!workspace) return EKS_ERR_WORKSPACE;
-  if (workspace_bytes < eks_innovations_workspace_bytes(d)) return EKS_ERR_WORKSPACE;
+  else if ((d->flags & EKS_FLAG_DIAG_MODEL) && (nis || frame_ll)) rest = EKS_ERR_UNSUPPORTED;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
-    return diag_innovations(*d, y, var, M, innov, innov_var, loglik, workspace, workspace_bytes, st);
-  }
-  const DenseModel M{m0, S0, A, C, Q, s};
-  return dense_innovations(*d, y, var, M, innov, innov_var, nis, frame_ll, loglik, workspace, workspace_bytes, st);
+  return model_call(
+      d, {y, var, m0, S0, A, C, Q, s}, rest,
+      [&](const DiagModel& M) {
+        return diag_innovations(*d, y, var, M, innov, innov_var, loglik, workspace, workspace_bytes, st);
+      },
+      [&](const DenseModel& M) {
+        return dense_innovations(*d, y, var, M, innov, innov_var, nis, frame_ll, loglik, workspace, workspace_bytes, st);
+      });
 }
 
 // shapes the M-step for the scale takes: eks_em_stats' with T >= 2 (n = D (T - 1) divides) and, on general models,
@@ -313,12 +320,14 @@ int32_t eks_sample_noise_width(const eks_dims_t* d) {
 }
 
 size_t eks_sample_workspace_bytes(const eks_dims_t* d, int32_t n_draws) {
-  if (check_dims(d) != EKS_OK || n_draws < 1) return 0;
-  if (d->flags & EKS_FLAG_DIAG_MODEL)
-    return diag_sample_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim, n_draws);
-  if (d->state_dim > 6 || d->obs_dim > 64) return 0;
-  if (((size_t)n_draws + 1) * d->n_keypoints * d->state_dim > (1u << 24)) return 0;   // eks_sample: EKS_ERR_SHAPE
-  return dense_sample_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim, n_draws);
+  return model_bytes(
+      d, n_draws < 1 ? EKS_ERR_SHAPE : check_dims(d),
+      [&](int T, int N) { return diag_sample_workspace_bytes(T, N, n_draws); },
+      [&](int T, int K, int D, int O) -> size_t {
+        if (D > 6 || O > 64) return 0;
+        if (((size_t)n_draws + 1) * K * D > (1u << 24)) return 0;   // eks_sample: EKS_ERR_SHAPE
+        return dense_sample_workspace_bytes(T, K, D, O, n_draws);
+      });
 }
 
 int eks_sample(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
@@ -328,17 +337,17 @@ int eks_sample(const eks_dims_t* d, const float* y, const float* var, const doub
   const int rc = check_dims(d);
   if (rc != EKS_OK) return rc;
   if (n_draws < 1 || first_keypoint < 0 || first_draw < 0) return EKS_ERR_SHAPE;
-  if (!y || !var || !m0 || !S0 || !A || !C || !Q || !s || !draws) return EKS_ERR_NULL;
-  if (!workspace) return EKS_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, s, d->state_dim};
-    return diag_sample(*d, y, var, M, n_draws, seed, first_keypoint, first_draw, noise, ms, draws, workspace,
-                       workspace_bytes, st);
-  }
-  const DenseModel M{m0, S0, A, C, Q, s};
-  return dense_sample(*d, y, var, M, n_draws, seed, first_keypoint, first_draw, noise, ms, draws, workspace,
-                      workspace_bytes, st);
+  return model_call(
+      d, {y, var, m0, S0, A, C, Q, s}, !draws ? EKS_ERR_NULL : workspace_status(workspace, workspace_bytes),
+      [&](const DiagModel& M) {
+        return diag_sample(*d, y, var, M, n_draws, seed, first_keypoint, first_draw, noise, ms, draws, workspace,
+                           workspace_bytes, st);
+      },
+      [&](const DenseModel& M) {
+        return dense_sample(*d, y, var, M, n_draws, seed, first_keypoint, first_draw, noise, ms, draws, workspace,
+                            workspace_bytes, st);
+      });
 }
 
 int eks_sample_noise(const eks_dims_t* d, int32_t n_draws, uint64_t seed, int32_t first_keypoint, int32_t first_draw,
@@ -373,11 +382,13 @@ int eks_const_r(const eks_dims_t* d, const float* var, double min_var, double* r
 }
 
 size_t eks_nll_workspace_bytes(const eks_dims_t* d, int32_t n_cand) {
-  if (check_dims(d) != EKS_OK || n_cand <= 0) return 0;
-  if (d->flags & EKS_FLAG_DIAG_MODEL)
-    return diag_nll_workspace_bytes(d->n_frames, d->n_keypoints * d->state_dim, n_cand);
-  return dense_nll_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim, n_cand);
+  return model_bytes(
+      d, n_cand <= 0 ? EKS_ERR_SHAPE : check_dims(d), [&](int T, int N) { return diag_nll_workspace_bytes(T, N, n_cand); },
+      [&](int T, int K, int D, int O) { return dense_nll_workspace_bytes(T, K, D, O, n_cand); });
 }
+
+// (the NLL entries: rconst in the place of var and the candidates in the place of s for the null test; the model the
+//  kernels get has no s, as in eks_adam_run)
 
 int eks_nll(const eks_dims_t* d, const float* y, const double* rconst, const double* m0,
             const double* S0, const double* A, const double* C, const double* Q,
@@ -386,17 +397,17 @@ int eks_nll(const eks_dims_t* d, const float* y, const double* rconst, const dou
   const int rc = check_dims(d);
   if (rc != EKS_OK) return rc;
   if (n_cand <= 0) return EKS_ERR_SHAPE;
-  if (!y || !rconst || !m0 || !S0 || !A || !C || !Q || !s_cand || !nll) return EKS_ERR_NULL;
-  if (!workspace) return EKS_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, nullptr, d->state_dim};
-    return diag_nll(*d, y, rconst, M, s_cand, n_cand, per_keypoint, nll, dnll, workspace,
-                    workspace_bytes, st);
-  }
-  const DenseModel M{m0, S0, A, C, Q, nullptr};
-  return dense_nll(*d, y, rconst, M, s_cand, n_cand, per_keypoint, nll, dnll, workspace,
-                   workspace_bytes, st);
+  return model_call(
+      d, {y, rconst, m0, S0, A, C, Q, s_cand}, !nll ? EKS_ERR_NULL : workspace_status(workspace, workspace_bytes),
+      [&](DiagModel M) {
+        M.s = nullptr;
+        return diag_nll(*d, y, rconst, M, s_cand, n_cand, per_keypoint, nll, dnll, workspace, workspace_bytes, st);
+      },
+      [&](DenseModel M) {
+        M.s = nullptr;
+        return dense_nll(*d, y, rconst, M, s_cand, n_cand, per_keypoint, nll, dnll, workspace, workspace_bytes, st);
+      });
 }
 
 int eks_nll_argmin(const eks_dims_t* d, const float* y, const double* rconst, const double* m0,
@@ -406,18 +417,21 @@ int eks_nll_argmin(const eks_dims_t* d, const float* y, const double* rconst, co
   const int rc = check_dims(d);
   if (rc != EKS_OK) return rc;
   if (n_cand <= 0) return EKS_ERR_SHAPE;
-  if (!y || !rconst || !m0 || !S0 || !A || !C || !Q || !s_cand || !nll || !s_out) return EKS_ERR_NULL;
-  if (!workspace) return EKS_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->flags & EKS_FLAG_DIAG_MODEL) {
-    const DiagModel M{m0, S0, A, C, Q, nullptr, d->state_dim};
-    return diag_nll(*d, y, rconst, M, s_cand, n_cand, 0, nll, nullptr, workspace, workspace_bytes, st, nullptr, s_out,
-                    idx_out);
-  }
-  const DenseModel M{m0, S0, A, C, Q, nullptr};
-  const int rc2 = dense_nll(*d, y, rconst, M, s_cand, n_cand, 0, nll, nullptr, workspace, workspace_bytes, st);
-  if (rc2 != EKS_OK) return rc2;
-  return argmin_s(d->n_keypoints, n_cand, nll, s_cand, s_out, idx_out, st);
+  return model_call(
+      d, {y, rconst, m0, S0, A, C, Q, s_cand},
+      !nll || !s_out ? EKS_ERR_NULL : workspace_status(workspace, workspace_bytes),
+      [&](DiagModel M) {
+        M.s = nullptr;
+        return diag_nll(*d, y, rconst, M, s_cand, n_cand, 0, nll, nullptr, workspace, workspace_bytes, st, nullptr, s_out,
+                        idx_out);
+      },
+      [&](DenseModel M) {
+        M.s = nullptr;
+        const int rc2 = dense_nll(*d, y, rconst, M, s_cand, n_cand, 0, nll, nullptr, workspace, workspace_bytes, st);
+        if (rc2 != EKS_OK) return rc2;
+        return argmin_s(d->n_keypoints, n_cand, nll, s_cand, s_out, idx_out, st);
+      });
 }
 
 int eks_order_stats(int32_t n_rows, int32_t n_cols, const float* x, int32_t rank_lo, int32_t rank_hi,

@@ -20,7 +20,7 @@ from typing import Literal
 import numpy as np
 
 from . import hip_ops
-from .posterior import _host_flags, _validate
+from ._problem import linear_problem, singlecam_problem, to_caller
 
 __all__ = ['filter_innovations', 'log_likelihood', 'innovation_summary', 'innovations_singlecam', 'FilterInnovations']
 
@@ -29,19 +29,14 @@ FilterInnovations = namedtuple('FilterInnovations', ['innov', 'innov_var', 'nis'
 
 def _run(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, h_fn, what, want):
     """-> (dict of device tensors in the kernels' frame-major layout, diag_model, O)."""
-    if h_fn is not None:
-        raise NotImplementedError(f'{what} covers linear models; h_fn models are not supported')
-    K, T, O, D, s = _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, 1, None, 0, 0)
-    flags = _host_flags(S0s, As, Cs, Qs)
+    L = linear_problem(what, ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, h_fn)
     from . import _lib
-    from .core import _DeviceProblem, _torch
-    torch = _torch()
-    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
+    P, s_dev = L.upload()
     diag_model = bool(P.flags & _lib.FLAG_DIAG_MODEL)
     if diag_model:      # nis and frame_ll are elementwise functions of innov and innov_var there: formed by torch
         want = tuple(w for w in want if w not in ('nis', 'frame_ll'))
-    out = hip_ops.innovations(P.y, P.var, *P.params, torch.as_tensor(s, device=P.dev), flags=P.flags, want=want)
-    return out, diag_model, O
+    out = hip_ops.innovations(P.y, P.var, *P.params, s_dev, flags=P.flags, want=want)
+    return out, diag_model, L.O
 
 
 def filter_innovations(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, return_device: bool = False,
@@ -57,7 +52,7 @@ def filter_innovations(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, ret
     the kernels' frame-major buffers, like run_kalman_smoother's."""
     out, diag_model, O = _run(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, h_fn, 'filter_innovations',
                               hip_ops.INNOVATION_OUTPUTS)
-    from .core import _to_host, _torch
+    from .core import _torch
     torch = _torch()
     loglik = out['loglik']
     if diag_model:
@@ -67,11 +62,8 @@ def filter_innovations(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, ret
         loglik = loglik.sum(dim=-1)
     else:
         nis, frame_ll = out['nis'], out['frame_ll']
-    res = (out['innov'], out['innov_var'], nis, frame_ll)
-    if return_device:
-        return FilterInnovations(*(a.transpose(0, 1) for a in res), loglik)
-    host = _to_host(*res)
-    return FilterInnovations(*(np.swapaxes(a, 0, 1) for a in host), loglik.cpu().numpy())
+    res = to_caller(return_device, (out['innov'], out['innov_var'], nis, frame_ll))
+    return FilterInnovations(*res, loglik if return_device else loglik.cpu().numpy())
 
 
 def log_likelihood(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, return_device: bool = False, h_fn=None):
@@ -111,19 +103,7 @@ def innovations_singlecam(marker_array, keypoint_names: list, s_finals, *,
         nis (T, K) float32    z_x^2 + z_y^2
         loglik (K,) float64   log-likelihood of the keypoint's centred ensemble means
     s_finals: the smoothing parameters the driver returned."""
-    from .core import ensemble
-    from .singlecam_smoother import initialize_kalman_filter
-    from .utils import center_predictions
-    M, V, T, K, _ = marker_array.shape
-    if V != 1:
-        raise ValueError('innovations_singlecam takes a single-view marker array')
-    if len(keypoint_names) != K:
-        raise ValueError(f'{len(keypoint_names)} keypoint names for {K} keypoints')
-    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)
-    _, centered, _, _ = center_predictions(ens, quantile_keep_pca=100)
-    stats = np.asarray(ens.array)[0, 0]
-    cen = np.asarray(centered.array)[0, 0]
-    m0s, S0s, As, Qs, Cs = initialize_kalman_filter(centered)
-    fi = filter_innovations(np.swapaxes(cen, 0, 1), m0s, S0s, As, Cs, Qs, stats[:, :, 2:4], s_finals)
+    model, _, _ = singlecam_problem('innovations_singlecam', marker_array, keypoint_names, avg_mode, var_mode)
+    fi = filter_innovations(*model, s_finals)
     z = np.swapaxes(fi.innov / np.sqrt(fi.innov_var), 0, 1)
     return dict(z=np.ascontiguousarray(z), nis=np.ascontiguousarray(np.swapaxes(fi.nis, 0, 1)), loglik=fi.loglik)

@@ -17,7 +17,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import hip_ops
-from .posterior import _host_flags, _validate
+from ._problem import linear_problem
 
 __all__ = ['process_noise_statistics', 'refine_smooth_param_em', 'fit_process_noise_em']
 
@@ -25,12 +25,10 @@ EM_STRIDE = 8      # iterations enqueued between two reads of the count of block
 
 
 def _problem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s, h_fn, what):
-    if h_fn is not None:
-        raise NotImplementedError(f'{what} covers linear models; h_fn models are not supported')
-    K, T, O, D, s = _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s, 1, None, 0, 0)
-    if not np.all(np.isfinite(s)) or np.any(s <= 0):
+    L = linear_problem(what, ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s, h_fn)
+    if not np.all(np.isfinite(L.s)) or np.any(L.s <= 0):
         raise ValueError('the smoothing parameters must be positive and finite')
-    return K, T, O, D, s, _host_flags(S0s, As, Cs, Qs)
+    return L
 
 
 def process_noise_statistics(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s, *, return_device: bool = False, h_fn=None):
@@ -41,16 +39,15 @@ def process_noise_statistics(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s, *, retu
     diagonal models (S0, A, C, Q all diagonal) only the diagonal is computed and the off-diagonal entries are returned
     as zeros: they are sums of products of the coordinates' means, which tr(Q^-1 Sw) with a diagonal Q never reads.
     One smoothing pass; T = 1 gives zeros."""
-    K, T, O, D, s, flags = _problem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s, h_fn, 'process_noise_statistics')
+    L = _problem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s, h_fn, 'process_noise_statistics')
     from . import _lib
-    from .core import _DeviceProblem, _torch
-    torch = _torch()
-    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
+    from .core import _torch
+    P, s_dev = L.upload()
     diag_model = bool(P.flags & _lib.FLAG_DIAG_MODEL)
-    Sw = hip_ops.em_stats(P.y, P.var, *P.params, torch.as_tensor(s, device=P.dev), flags=P.flags, vs_diag=diag_model)
+    Sw = hip_ops.em_stats(P.y, P.var, *P.params, s_dev, flags=P.flags, vs_diag=diag_model)
     if diag_model:
-        Sw = torch.diag_embed(Sw)
-    return (Sw if return_device else Sw.cpu().numpy()), D * (T - 1)
+        Sw = _torch().diag_embed(Sw)
+    return (Sw if return_device else Sw.cpu().numpy()), L.D * (L.T - 1)
 
 
 def refine_smooth_param_em(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_init, *, blocks: list | None = None,
@@ -69,7 +66,8 @@ def refine_smooth_param_em(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_init, *, b
     numerators and denominators.  A block stops when |delta log s| < tol or after max_iters iterations; log s is kept
     inside s_bounds_log.  Returns s_finals (K,) float64; with return_info also a dict of per-block arrays
     `iterations`, `last_delta_log_s`, `done`.  General models need a well-conditioned positive definite Q."""
-    K, T, O, D, s, flags = _problem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_init, h_fn, 'refine_smooth_param_em')
+    L = _problem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_init, h_fn, 'refine_smooth_param_em')
+    K, T, s, flags = L.K, L.T, L.s, L.flags
     if T < 2:
         raise ValueError('EM for the scale needs at least two frames')
     if int(max_iters) != max_iters or max_iters < 0:
@@ -78,7 +76,7 @@ def refine_smooth_param_em(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_init, *, b
     if not lo < hi:
         raise ValueError('s_bounds_log must be (lo, hi) with lo < hi')
     from . import _lib
-    from .core import _DeviceProblem, _block_csr, _torch
+    from .core import _block_csr, _torch
     offs, members, of_kp = _block_csr(blocks if blocks else None, K)
     if not (flags & _lib.FLAG_DIAG_MODEL) and not (flags & _lib.FLAG_Q_PD):
         raise ValueError('refine_smooth_param_em needs a positive definite Q with cond(Q) <= 1e6 on general models')
@@ -87,7 +85,7 @@ def refine_smooth_param_em(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_init, *, b
     state = np.zeros((nb, 4))
     state[:, 0] = log_s
     torch = _torch()
-    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
+    P, _ = L.upload()
     loop = hip_ops.EmScaleLoop(P.y, P.var, *P.params, torch.as_tensor(offs, device=P.dev),
                                torch.as_tensor(members, device=P.dev), torch.as_tensor(state, device=P.dev),
                                torch.as_tensor(np.exp(log_s)[of_kp], device=P.dev), lo, hi, tol, int(max_iters),
@@ -113,16 +111,16 @@ def fit_process_noise_em(ys, m0s, S0s, As, Cs, Qs_init, ensemble_vars, *, max_it
     decrease the likelihood.  Stops when every keypoint's relative Frobenius change of Q is below tol, or after
     max_iters iterations.  Diagonal models (S0, A, C, Q all diagonal) keep Q diagonal.  Returns Qs (K, D, D) float64.
     Like every EM it is slow from a distant start."""
-    K, T, O, D, s, flags = _problem(ys, m0s, S0s, As, Cs, Qs_init, ensemble_vars, 1.0, h_fn, 'fit_process_noise_em')
+    L = _problem(ys, m0s, S0s, As, Cs, Qs_init, ensemble_vars, 1.0, h_fn, 'fit_process_noise_em')
+    T = L.T
     if T < 2:
         raise ValueError('EM for Q needs at least two frames')
     from . import _lib
-    from .core import _DeviceProblem, _torch
+    from .core import _torch
     torch = _torch()
-    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs_init, ensemble_vars, flags=flags)
+    P, ones = L.upload()
     diag_model = bool(P.flags & _lib.FLAG_DIAG_MODEL)
     Q = P.params[4]
-    ones = torch.as_tensor(s, device=P.dev)
     for _ in range(int(max_iters)):
         Sw = hip_ops.em_stats(P.y, P.var, *P.params, ones, flags=P.flags, vs_diag=diag_model)
         Qn = torch.diag_embed(Sw) if diag_model else 0.5 * (Sw + Sw.transpose(1, 2))

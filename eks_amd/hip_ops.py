@@ -104,6 +104,34 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _model_args(y, r, m0, S0, A, C, Q, *s, r_is='var'):
+    """The linear-Gaussian model's arguments, checked in the C order -> ((T, K, O, D), [y, r, m0, S0, A, C, Q(, s)]).
+    r is var (T, K, O) float32, or with r_is='rconst' the constant noise (K, O) float64; r_is=None leaves it out (None
+    in its place: AdamLoop is given its rconst later).  s (K,) float64 follows where the entry takes one."""
+    T, K, O = y.shape
+    D = m0.shape[-1]
+    bufs = [_chk(y, torch.float32, 'y'),
+            _chk(r, torch.float32, 'var', (T, K, O)) if r_is == 'var' else
+            _chk(r, torch.float64, 'rconst', (K, O)) if r_is == 'rconst' else None,
+            _chk(m0, torch.float64, 'm0', (K, D)), _chk(S0, torch.float64, 'S0', (K, D, D)),
+            _chk(A, torch.float64, 'A', (K, D, D)), _chk(C, torch.float64, 'C', (K, O, D)),
+            _chk(Q, torch.float64, 'Q', (K, D, D))]
+    for t in s:
+        bufs.append(_chk(t, torch.float64, 's', (K,)))
+    return (T, K, O, D), bufs
+
+
+def _vs_flags(flags: int, vs_diag: bool) -> int:
+    """flags with FLAG_VS_DIAG set for vs_diag and cleared without (PreparedSmooth alone only ever sets it)."""
+    return flags | FLAG_VS_DIAG if vs_diag else flags & ~FLAG_VS_DIAG
+
+
+def _ms_Vs(T, K, D, vs_diag: bool, device):
+    """The smoother's outputs: ms (T, K, D) and Vs (T, K, D, D), or its diagonal (T, K, D) with vs_diag."""
+    return (torch.empty((T, K, D), dtype=torch.float32, device=device),
+            torch.empty((T, K, D) if vs_diag else (T, K, D, D), dtype=torch.float32, device=device))
+
+
 Q_PD_MIN_EIG_RATIO = 1e-6      # EKS_FLAG_Q_PD is asserted for cond(Q) <= 1e6 (every keypoint)
 
 
@@ -162,6 +190,8 @@ class PreparedSmooth:
     costs 19 us per `smooth()` call on the host but 12.5 us through this object (tools/c2_host_time.py)."""
 
     def __init__(self, y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False, out=None):
+        # (_model_args, _vs_flags and _ms_Vs written out: smooth() builds one of these per call, and the helpers' calls
+        #  were 2 us of its 17 us on configs[1] - DESIGN.md 9m)
         lib = _lib.load()
         T, K, O = y.shape
         D = m0.shape[-1]
@@ -174,7 +204,7 @@ class PreparedSmooth:
         Q = _chk(Q, torch.float64, 'Q', (K, D, D))
         s = _chk(s, torch.float64, 's', (K,))
         if vs_diag:
-            flags |= FLAG_VS_DIAG
+            flags |= FLAG_VS_DIAG                               # (only ever set: a bit the caller's flags carry stays)
         self._dims = _dims(K, T, D, O, flags)
         if out is None:
             ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device)
@@ -206,20 +236,41 @@ def smooth_tv(y, var, qscale, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool 
     entry 0 is never read.  The precondition 0 <= w <= 1e6, finite, is the caller's (eks_amd.irregular enforces it).
     Returns (ms, Vs) as smooth()."""
     lib = _lib.load()
-    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
-    s = _chk(s, torch.float64, 's', (K,))
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
     if qscale.dim() not in (1, 2):
         raise ValueError(f'qscale must have shape {(T,)} or {(T, K)}, got {tuple(qscale.shape)}')
     qscale = _chk(qscale, torch.float32, 'qscale', (T,) if qscale.dim() == 1 else (T, K))
-    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
-    dims = _dims(K, T, D, O, flags)
-    ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device)
-    Vs = torch.empty((T, K, D) if vs_diag else (T, K, D, D), dtype=torch.float32, device=y.device)
+    dims = _dims(K, T, D, O, _vs_flags(flags, vs_diag))
+    ms, Vs = _ms_Vs(T, K, D, vs_diag, y.device)
     ws = _workspace(lib.eks_smooth_tv_workspace_bytes(ctypes.byref(dims)), y.device)
     rc = lib.eks_smooth_tv(ctypes.byref(dims), _ptr(bufs[0]), _ptr(bufs[1]), _ptr(qscale), int(qscale.dim() == 2),
-                           *[_ptr(b) for b in bufs[2:]], _ptr(s), _ptr(ms), _ptr(Vs), _ptr(ws), ws.numel(), _stream())
+                           *[_ptr(b) for b in bufs[2:]], _ptr(ms), _ptr(Vs), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, 'eks_smooth_tv')
     return ms, Vs
+
+
+def _smooth_iterated(entry, plane_name, per_coordinate, model, nu, n_iters, flags, vs_diag, plane, plane_in, want_change):
+    """The body of smooth_robust and smooth_jumps: `plane` is the weights (T, K, O) of the one (per_coordinate) and the
+    scales (T, K) of the other."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _model_args(*model)
+    dev = bufs[0].device
+    if plane_in and plane is None:
+        raise ValueError(f'{plane_name}_in needs a {plane_name} tensor')
+    shape = (T, K, O) if per_coordinate else (T, K)
+    if plane is None:
+        plane = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not plane.is_contiguous():
+        raise ValueError(f'{plane_name} must be contiguous: it is written in place')
+    plane = _chk(plane, torch.float32, plane_name, shape)
+    dims = _dims(K, T, D, O, _vs_flags(flags, vs_diag))
+    ms, Vs = _ms_Vs(T, K, D, vs_diag, dev)
+    change = torch.empty((K,), dtype=torch.float32, device=dev) if want_change else None
+    ws = _workspace(getattr(lib, entry + '_workspace_bytes')(ctypes.byref(dims)), dev)
+    rc = getattr(lib, entry)(ctypes.byref(dims), *[_ptr(b) for b in bufs], float(nu), int(n_iters), _ptr(plane),
+                             int(bool(plane_in)), _ptr(change), _ptr(ms), _ptr(Vs), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, entry)
+    return ms, Vs, plane, change
 
 
 def smooth_robust(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 8, flags: int = 0, vs_diag: bool = False,
@@ -229,27 +280,8 @@ def smooth_robust(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 8,
     (T, K, O) that receives the weights; with weights_in the first pass starts from its contents.  Returns
     (ms, Vs, weights, change): change is (K,) float32, the largest weight change of the last update (None without
     want_change)."""
-    lib = _lib.load()
-    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
-    s = _chk(s, torch.float64, 's', (K,))
-    if weights_in and weights is None:
-        raise ValueError('weights_in needs a weights tensor')
-    if weights is None:
-        weights = torch.empty((T, K, O), dtype=torch.float32, device=y.device)
-    elif not weights.is_contiguous():
-        raise ValueError('weights must be contiguous: it is written in place')
-    weights = _chk(weights, torch.float32, 'weights', (T, K, O))
-    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
-    dims = _dims(K, T, D, O, flags)
-    ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device)
-    Vs = torch.empty((T, K, D) if vs_diag else (T, K, D, D), dtype=torch.float32, device=y.device)
-    change = torch.empty((K,), dtype=torch.float32, device=y.device) if want_change else None
-    ws = _workspace(lib.eks_smooth_robust_workspace_bytes(ctypes.byref(dims)), y.device)
-    rc = lib.eks_smooth_robust(ctypes.byref(dims), *[_ptr(b) for b in bufs], _ptr(s), float(nu), int(n_iters),
-                               _ptr(weights), int(bool(weights_in)), _ptr(change), _ptr(ms), _ptr(Vs), _ptr(ws),
-                               ws.numel(), _stream())
-    _lib.check(rc, 'eks_smooth_robust')
-    return ms, Vs, weights, change
+    return _smooth_iterated('eks_smooth_robust', 'weights', True, (y, var, m0, S0, A, C, Q, s), nu, n_iters, flags,
+                            vs_diag, weights, weights_in, want_change)
 
 
 def smooth_jumps(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 12, flags: int = 0, vs_diag: bool = False,
@@ -259,27 +291,8 @@ def smooth_jumps(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 12,
     float32 device tensor (T, K) that receives the scales - eks_smooth_tv's per-keypoint qscale; with scales_in the
     first pass starts from its contents.  Returns (ms, Vs, scales, change): change is (K,) float32, the largest
     change of u = 1 / scale in the last update (None without want_change)."""
-    lib = _lib.load()
-    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
-    s = _chk(s, torch.float64, 's', (K,))
-    if scales_in and scales is None:
-        raise ValueError('scales_in needs a scales tensor')
-    if scales is None:
-        scales = torch.empty((T, K), dtype=torch.float32, device=y.device)
-    elif not scales.is_contiguous():
-        raise ValueError('scales must be contiguous: it is written in place')
-    scales = _chk(scales, torch.float32, 'scales', (T, K))
-    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
-    dims = _dims(K, T, D, O, flags)
-    ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device)
-    Vs = torch.empty((T, K, D) if vs_diag else (T, K, D, D), dtype=torch.float32, device=y.device)
-    change = torch.empty((K,), dtype=torch.float32, device=y.device) if want_change else None
-    ws = _workspace(lib.eks_smooth_jumps_workspace_bytes(ctypes.byref(dims)), y.device)
-    rc = lib.eks_smooth_jumps(ctypes.byref(dims), *[_ptr(b) for b in bufs], _ptr(s), float(nu), int(n_iters),
-                              _ptr(scales), int(bool(scales_in)), _ptr(change), _ptr(ms), _ptr(Vs), _ptr(ws),
-                              ws.numel(), _stream())
-    _lib.check(rc, 'eks_smooth_jumps')
-    return ms, Vs, scales, change
+    return _smooth_iterated('eks_smooth_jumps', 'scales', False, (y, var, m0, S0, A, C, Q, s), nu, n_iters, flags,
+                            vs_diag, scales, scales_in, want_change)
 
 
 def smooth_increments(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False,
@@ -289,53 +302,32 @@ def smooth_increments(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool 
     tensors: ms (T, K, D) and Vs (unless want_smooth is False) and the outputs named in `want`; Vs, lag1, dV are
     (T, K, D) diagonals with vs_diag, (T, K, D, D) without.  Scalar chains (FLAG_DIAG_MODEL) exist with vs_diag only."""
     lib = _lib.load()
-    T, K, O = y.shape
-    D = m0.shape[-1]
     want = tuple(want)
     if not want or any(w not in ('lag1', 'dmean', 'dV') for w in want):
         raise ValueError("want must name at least one of 'lag1', 'dmean', 'dV'")
-    y = _chk(y, torch.float32, 'y')
-    var = _chk(var, torch.float32, 'var', (T, K, O))
-    m0 = _chk(m0, torch.float64, 'm0', (K, D))
-    S0 = _chk(S0, torch.float64, 'S0', (K, D, D))
-    A = _chk(A, torch.float64, 'A', (K, D, D))
-    C = _chk(C, torch.float64, 'C', (K, O, D))
-    Q = _chk(Q, torch.float64, 'Q', (K, D, D))
-    s = _chk(s, torch.float64, 's', (K,))
-    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
-    dims = _dims(K, T, D, O, flags)
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
+    dims = _dims(K, T, D, O, _vs_flags(flags, vs_diag))
     cov = (T, K, D) if vs_diag else (T, K, D, D)
     shapes = dict(ms=(T, K, D), Vs=cov, lag1=cov, dmean=(T, K, D), dV=cov)
     names = (('ms', 'Vs') if want_smooth else ()) + want
     out = {n: torch.empty(shapes[n], dtype=torch.float32, device=y.device) for n in shapes if n in names}
     ws = _workspace(lib.eks_smooth_increments_workspace_bytes(ctypes.byref(dims)), y.device)
-    rc = lib.eks_smooth_increments(ctypes.byref(dims), _ptr(y), _ptr(var), _ptr(m0), _ptr(S0), _ptr(A), _ptr(C), _ptr(Q),
-                                   _ptr(s), *(_ptr(out.get(n)) for n in ('ms', 'Vs', 'lag1', 'dmean', 'dV')), _ptr(ws),
+    rc = lib.eks_smooth_increments(ctypes.byref(dims), *[_ptr(b) for b in bufs],
+                                   *(_ptr(out.get(n)) for n in ('ms', 'Vs', 'lag1', 'dmean', 'dV')), _ptr(ws),
                                    ws.numel(), _stream())
     _lib.check(rc, 'eks_smooth_increments')
     return out
-
-
-def _em_args(y, var, m0, S0, A, C, Q):
-    T, K, O = y.shape
-    D = m0.shape[-1]
-    return (T, K, O, D), [_chk(y, torch.float32, 'y'), _chk(var, torch.float32, 'var', (T, K, O)),
-                          _chk(m0, torch.float64, 'm0', (K, D)), _chk(S0, torch.float64, 'S0', (K, D, D)),
-                          _chk(A, torch.float64, 'A', (K, D, D)), _chk(C, torch.float64, 'C', (K, O, D)),
-                          _chk(Q, torch.float64, 'Q', (K, D, D))]
 
 
 def em_stats(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False):
     """eks_em_stats: Sw = sum_t E[w_t w_t' | y] of the model eks_smooth runs, float64 (K, D) with vs_diag (the only
     form on scalar chains, FLAG_DIAG_MODEL) or (K, D, D)."""
     lib = _lib.load()
-    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
-    s = _chk(s, torch.float64, 's', (K,))
-    flags = (flags | FLAG_VS_DIAG) if vs_diag else (flags & ~FLAG_VS_DIAG)
-    dims = _dims(K, T, D, O, flags)
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
+    dims = _dims(K, T, D, O, _vs_flags(flags, vs_diag))
     Sw = torch.empty((K, D) if vs_diag else (K, D, D), dtype=torch.float64, device=y.device)
     ws = _workspace(lib.eks_em_stats_workspace_bytes(ctypes.byref(dims)), y.device)
-    rc = lib.eks_em_stats(ctypes.byref(dims), *[_ptr(b) for b in bufs], _ptr(s), _ptr(Sw), _ptr(ws), ws.numel(), _stream())
+    rc = lib.eks_em_stats(ctypes.byref(dims), *[_ptr(b) for b in bufs], _ptr(Sw), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, 'eks_em_stats')
     return Sw
 
@@ -349,8 +341,7 @@ def innovations(y, var, m0, S0, A, C, Q, s, flags: int = 0, want=INNOVATION_OUTP
     models only: on scalar chains, FLAG_DIAG_MODEL, the library refuses them); loglik float64, (K, D) per chain on
     scalar chains and (K,) on general models."""
     lib = _lib.load()
-    (T, K, O, D), bufs = _em_args(y, var, m0, S0, A, C, Q)
-    s = _chk(s, torch.float64, 's', (K,))
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
     want = tuple(want)
     if not want or any(w not in INNOVATION_OUTPUTS for w in want):
         raise ValueError(f'want must name at least one of {INNOVATION_OUTPUTS}')
@@ -360,7 +351,7 @@ def innovations(y, var, m0, S0, A, C, Q, s, flags: int = 0, want=INNOVATION_OUTP
     out = {n: torch.empty(shapes[n], dtype=torch.float64 if n == 'loglik' else torch.float32, device=y.device)
            for n in INNOVATION_OUTPUTS if n in want}
     ws = _workspace(lib.eks_innovations_workspace_bytes(ctypes.byref(dims)), y.device)
-    rc = lib.eks_innovations(ctypes.byref(dims), *[_ptr(b) for b in bufs], _ptr(s),
+    rc = lib.eks_innovations(ctypes.byref(dims), *[_ptr(b) for b in bufs],
                              *(_ptr(out.get(n)) for n in INNOVATION_OUTPUTS), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, 'eks_innovations')
     return out
@@ -375,7 +366,7 @@ class EmScaleLoop:
     def __init__(self, y, var, m0, S0, A, C, Q, block_offsets, block_members, state, s_keypoint, lo, hi, tol,
                  max_iters, flags: int = 0):
         self.lib = _lib.load()
-        (T, K, O, D), self.bufs = _em_args(y, var, m0, S0, A, C, Q)
+        (T, K, O, D), self.bufs = _model_args(y, var, m0, S0, A, C, Q)
         self.offs = _chk(block_offsets, torch.int32, 'block_offsets')
         self.members = _chk(block_members, torch.int32, 'block_members', (K,))
         self.nb = self.offs.numel() - 1
@@ -383,8 +374,7 @@ class EmScaleLoop:
         self.s_keypoint = _chk(s_keypoint, torch.float64, 's_keypoint', (K,))
         self.opt = (float(lo), float(hi), float(tol), int(max_iters))
         diag = bool(flags & FLAG_DIAG_MODEL)
-        flags = (flags | FLAG_VS_DIAG) if diag else (flags & ~FLAG_VS_DIAG)
-        self.dims = _dims(K, T, D, O, flags)
+        self.dims = _dims(K, T, D, O, _vs_flags(flags, diag))
         dev = y.device
         self.Sw = torch.zeros((K, D) if diag else (K, D, D), dtype=torch.float64, device=dev)
         self.n_active = torch.full((1,), self.nb, dtype=torch.int32, device=dev)
@@ -415,30 +405,20 @@ def sample(y, var, m0, S0, A, C, Q, s, n_draws: int, seed: int = 0, flags: int =
     """eks_sample: n_draws joint posterior trajectories.  Returns (draws (n_draws, T, K, D) float32, ms (T, K, D) or
     None).  noise (n_draws, T, K, W) float32 replaces the generator; out: a preallocated draws tensor."""
     lib = _lib.load()
-    T, K, O = y.shape
-    D = m0.shape[-1]
     n_draws = int(n_draws)
     if n_draws < 1:
         raise ValueError('n_draws must be at least 1')
-    y = _chk(y, torch.float32, 'y')
-    var = _chk(var, torch.float32, 'var', (T, K, O))
-    m0 = _chk(m0, torch.float64, 'm0', (K, D))
-    S0 = _chk(S0, torch.float64, 'S0', (K, D, D))
-    A = _chk(A, torch.float64, 'A', (K, D, D))
-    C = _chk(C, torch.float64, 'C', (K, O, D))
-    Q = _chk(Q, torch.float64, 'Q', (K, D, D))
-    s = _chk(s, torch.float64, 's', (K,))
-    flags &= ~FLAG_VS_DIAG
-    dims = _dims(K, T, D, O, flags)
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
+    dims = _dims(K, T, D, O, _vs_flags(flags, False))
     if noise is not None:
         noise = _chk(noise, torch.float32, 'noise', (n_draws, T, K, lib.eks_sample_noise_width(ctypes.byref(dims))))
     draws = torch.empty((n_draws, T, K, D), dtype=torch.float32, device=y.device) if out is None \
         else _chk(out, torch.float32, 'out', (n_draws, T, K, D))
     ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device) if want_mean else None
     ws = _workspace(lib.eks_sample_workspace_bytes(ctypes.byref(dims), n_draws), y.device)
-    rc = lib.eks_sample(ctypes.byref(dims), _ptr(y), _ptr(var), _ptr(m0), _ptr(S0), _ptr(A), _ptr(C), _ptr(Q), _ptr(s),
-                        n_draws, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_keypoint), int(first_draw), _ptr(noise),
-                        _ptr(ms), _ptr(draws), _ptr(ws), ws.numel(), _stream())
+    rc = lib.eks_sample(ctypes.byref(dims), *[_ptr(b) for b in bufs], n_draws, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                        int(first_keypoint), int(first_draw), _ptr(noise), _ptr(ms), _ptr(draws), _ptr(ws), ws.numel(),
+                        _stream())
     _lib.check(rc, 'eks_sample')
     return draws, ms
 
@@ -596,15 +576,7 @@ def nll(y, rconst, m0, S0, A, C, Q, s_cand, per_keypoint: bool = False, want_gra
     """eks_nll: constant-R filter NLL for candidate s values.  Returns nll (K, n_cand) float64 and
     (if want_grad) d nll / d log s of the same shape."""
     lib = _lib.load()
-    T, K, O = y.shape
-    D = m0.shape[-1]
-    y = _chk(y, torch.float32, 'y')
-    rconst = _chk(rconst, torch.float64, 'rconst', (K, O))
-    m0 = _chk(m0, torch.float64, 'm0', (K, D))
-    S0 = _chk(S0, torch.float64, 'S0', (K, D, D))
-    A = _chk(A, torch.float64, 'A', (K, D, D))
-    C = _chk(C, torch.float64, 'C', (K, O, D))
-    Q = _chk(Q, torch.float64, 'Q', (K, D, D))
+    (T, K, O, D), bufs = _model_args(y, rconst, m0, S0, A, C, Q, r_is='rconst')
     s_cand = _chk(s_cand, torch.float64, 's_cand')
     n_cand = s_cand.shape[-1]
     if per_keypoint and tuple(s_cand.shape) != (K, n_cand):
@@ -615,9 +587,8 @@ def nll(y, rconst, m0, S0, A, C, Q, s_cand, per_keypoint: bool = False, want_gra
     out = torch.empty((K, n_cand), dtype=torch.float64, device=y.device)
     grad = torch.empty((K, n_cand), dtype=torch.float64, device=y.device) if want_grad else None
     ws = _workspace(lib.eks_nll_workspace_bytes(ctypes.byref(d), n_cand), y.device)
-    rc = lib.eks_nll(ctypes.byref(d), _ptr(y), _ptr(rconst), _ptr(m0), _ptr(S0), _ptr(A), _ptr(C),
-                     _ptr(Q), _ptr(s_cand), n_cand, int(per_keypoint), _ptr(out), _ptr(grad),
-                     _ptr(ws), ws.numel(), _stream())
+    rc = lib.eks_nll(ctypes.byref(d), *[_ptr(b) for b in bufs], _ptr(s_cand), n_cand, int(per_keypoint), _ptr(out),
+                     _ptr(grad), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, 'eks_nll')
     return (out, grad) if want_grad else out
 
@@ -626,15 +597,7 @@ def nll_argmin(y, rconst, m0, S0, A, C, Q, s_cand, flags: int = 0):
     """eks_nll_argmin: the grid search in one call - the NLL table (K, n_cand), s at each keypoint's argmin and the
     int32 indices (the scalar-chain grid kernels take the argmin inside the table's assembly)."""
     lib = _lib.load()
-    T, K, O = y.shape
-    D = m0.shape[-1]
-    y = _chk(y, torch.float32, 'y')
-    rconst = _chk(rconst, torch.float64, 'rconst', (K, O))
-    m0 = _chk(m0, torch.float64, 'm0', (K, D))
-    S0 = _chk(S0, torch.float64, 'S0', (K, D, D))
-    A = _chk(A, torch.float64, 'A', (K, D, D))
-    C = _chk(C, torch.float64, 'C', (K, O, D))
-    Q = _chk(Q, torch.float64, 'Q', (K, D, D))
+    (T, K, O, D), bufs = _model_args(y, rconst, m0, S0, A, C, Q, r_is='rconst')
     s_cand = _chk(s_cand, torch.float64, 's_cand')
     if s_cand.dim() != 1:
         raise ValueError('s_cand must be (n_cand,)')
@@ -644,8 +607,8 @@ def nll_argmin(y, rconst, m0, S0, A, C, Q, s_cand, flags: int = 0):
     s_out = torch.empty(K, dtype=torch.float64, device=y.device)
     idx = torch.empty(K, dtype=torch.int32, device=y.device)
     ws = _workspace(lib.eks_nll_workspace_bytes(ctypes.byref(d), n_cand), y.device)
-    rc = lib.eks_nll_argmin(ctypes.byref(d), _ptr(y), _ptr(rconst), _ptr(m0), _ptr(S0), _ptr(A), _ptr(C), _ptr(Q),
-                            _ptr(s_cand), n_cand, _ptr(out), _ptr(s_out), _ptr(idx), _ptr(ws), ws.numel(), _stream())
+    rc = lib.eks_nll_argmin(ctypes.byref(d), *[_ptr(b) for b in bufs], _ptr(s_cand), n_cand, _ptr(out), _ptr(s_out),
+                            _ptr(idx), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, 'eks_nll_argmin')
     return out, s_out, idx
 
@@ -679,13 +642,8 @@ class AdamLoop:
     def __init__(self, y, rconst, m0, S0, A, C, Q, block_offsets, block_members, state, s_keypoint, lr,
                  lo, hi, tol, safety_cap, flags: int = 0):
         self.lib = _lib.load()
-        T, K, O = y.shape
-        D = m0.shape[-1]
         # (rconst may be given later - set_rconst - by a caller that enqueues prepare() before eks_const_r)
-        self.bufs = [_chk(y, torch.float32, 'y'), None if rconst is None else _chk(rconst, torch.float64, 'rconst', (K, O)),
-                     _chk(m0, torch.float64, 'm0', (K, D)), _chk(S0, torch.float64, 'S0', (K, D, D)),
-                     _chk(A, torch.float64, 'A', (K, D, D)), _chk(C, torch.float64, 'C', (K, O, D)),
-                     _chk(Q, torch.float64, 'Q', (K, D, D))]
+        (T, K, O, D), self.bufs = _model_args(y, rconst, m0, S0, A, C, Q, r_is=None if rconst is None else 'rconst')
         self.offs = _chk(block_offsets, torch.int32, 'block_offsets')
         self.members = _chk(block_members, torch.int32, 'block_members', (K,))
         self.nb = self.offs.numel() - 1
@@ -865,6 +823,31 @@ def pupil_adam_run(loss: Ar1Loss, latent_var, state, n_active, lr, tol, safety_c
     _lib.check(rc, 'eks_pupil_adam_run')
 
 
+def _ekf_args(y, var, rconst, m0, S0, A, Q, s, D):
+    """What ekf_smooth and ekf_affine_sweep take alike, checked -> ((T, Kd, O, K), (y, var, rconst, m0, S0, A, Q, s))."""
+    T, Kd, O = y.shape
+    K = m0.shape[0]
+    y = _chk(y, torch.float32, 'y')
+    if (var is None) == (rconst is None):
+        raise ValueError('pass exactly one of var and rconst')
+    if var is not None:
+        var = _chk(var, torch.float32, 'var', (T, Kd, O))
+    else:
+        rconst = _chk(rconst, torch.float64, 'rconst', (Kd, O))
+    return (T, Kd, O, K), (y, var, rconst, _chk(m0, torch.float64, 'm0', (K, D)), _chk(S0, torch.float64, 'S0', (K, D, D)),
+                           _chk(A, torch.float64, 'A', (K, D, D)), _chk(Q, torch.float64, 'Q', (K, D, D)),
+                           _chk(s, torch.float64, 's', (K,)))
+
+
+def _ekf_outputs(xlin, K, T, D, O, vs_diag, want_smoother):
+    """xlin checked (it is updated in place), then (dims, ms, Vs) with ms = Vs = None unless want_smoother."""
+    if not xlin.is_contiguous():
+        raise ValueError('xlin must be contiguous (it is updated in place)')
+    _chk(xlin, torch.float64, 'xlin', (K, T, D))
+    ms, Vs = _ms_Vs(T, K, D, vs_diag, xlin.device) if want_smoother else (None, None)
+    return _dims(K, T, D, O, FLAG_VS_DIAG if vs_diag else 0), ms, Vs
+
+
 def ekf_smooth(y, var, rconst, m0, S0, A, Q, s, cams, xlin, max_sweeps: int = 16, tol: float = 1e-9,
                want_smoother: bool = True, vs_diag: bool = False):
     """eks_ekf_smooth: extended Kalman filter (+ RTS smoother) with calibrated pinhole cameras.
@@ -875,30 +858,10 @@ def ekf_smooth(y, var, rconst, m0, S0, A, Q, s, cams, xlin, max_sweeps: int = 16
     Returns (ms, Vs, nll, info): ms / Vs are None when want_smoother is False; info is a device
     tensor (sweeps executed, last relative change of a linearisation point)."""
     lib = _lib.load()
-    T, Kd, O = y.shape
-    K = m0.shape[0]
     V = cams.shape[0]
-    y = _chk(y, torch.float32, 'y')
-    if (var is None) == (rconst is None):
-        raise ValueError('pass exactly one of var and rconst')
-    if var is not None:
-        var = _chk(var, torch.float32, 'var', (T, Kd, O))
-    else:
-        rconst = _chk(rconst, torch.float64, 'rconst', (Kd, O))
-    m0 = _chk(m0, torch.float64, 'm0', (K, 3))
-    S0 = _chk(S0, torch.float64, 'S0', (K, 3, 3))
-    A = _chk(A, torch.float64, 'A', (K, 3, 3))
-    Q = _chk(Q, torch.float64, 'Q', (K, 3, 3))
-    s = _chk(s, torch.float64, 's', (K,))
+    (T, Kd, O, K), (y, var, rconst, m0, S0, A, Q, s) = _ekf_args(y, var, rconst, m0, S0, A, Q, s, 3)
     cams = _chk(cams, torch.float64, 'cams', (V, 32))
-    if not xlin.is_contiguous():
-        raise ValueError('xlin must be contiguous (it is updated in place)')
-    _chk(xlin, torch.float64, 'xlin', (K, T, 3))
-    d = _dims(K, T, 3, O, FLAG_VS_DIAG if vs_diag else 0)
-    ms = Vs = None
-    if want_smoother:
-        ms = torch.empty((T, K, 3), dtype=torch.float32, device=y.device)
-        Vs = torch.empty((T, K, 3) if vs_diag else (T, K, 3, 3), dtype=torch.float32, device=y.device)
+    d, ms, Vs = _ekf_outputs(xlin, K, T, 3, O, vs_diag, want_smoother)
     nll_k = torch.empty((K,), dtype=torch.float64, device=y.device)
     info = torch.zeros((2,), dtype=torch.float64, device=y.device)
     ws = _workspace(lib.eks_ekf_smooth_workspace_bytes(ctypes.byref(d), int(want_smoother)), y.device)
@@ -928,32 +891,13 @@ def ekf_affine_sweep(y, var, rconst, m0, S0, A, Q, s, jac, off, xlin, want_smoot
     means.  ws: a workspace from ekf_affine_workspace (made here when None); nll (K,), change (1,) float64: optional
     output buffers.  Returns (ms, Vs, nll, change) as device tensors; ms / Vs are None when want_smoother is False."""
     lib = _lib.load()
-    T, Kd, O = y.shape
-    K, D = m0.shape
-    y = _chk(y, torch.float32, 'y')
-    if (var is None) == (rconst is None):
-        raise ValueError('pass exactly one of var and rconst')
-    if var is not None:
-        var = _chk(var, torch.float32, 'var', (T, Kd, O))
-    else:
-        rconst = _chk(rconst, torch.float64, 'rconst', (Kd, O))
-    m0 = _chk(m0, torch.float64, 'm0', (K, D))
-    S0 = _chk(S0, torch.float64, 'S0', (K, D, D))
-    A = _chk(A, torch.float64, 'A', (K, D, D))
-    Q = _chk(Q, torch.float64, 'Q', (K, D, D))
-    s = _chk(s, torch.float64, 's', (K,))
+    D = m0.shape[1]
+    (T, Kd, O, K), (y, var, rconst, m0, S0, A, Q, s) = _ekf_args(y, var, rconst, m0, S0, A, Q, s, D)
     if jac is not None:
         jac = _chk(jac, torch.float64, 'jac', (T, K, O, D))
     if off is not None:
         off = _chk(off, torch.float64, 'off', (T, K, O))
-    if not xlin.is_contiguous():
-        raise ValueError('xlin must be contiguous (it is updated in place)')
-    _chk(xlin, torch.float64, 'xlin', (K, T, D))
-    d = _dims(K, T, D, O, FLAG_VS_DIAG if vs_diag else 0)
-    ms = Vs = None
-    if want_smoother:
-        ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device)
-        Vs = torch.empty((T, K, D) if vs_diag else (T, K, D, D), dtype=torch.float32, device=y.device)
+    d, ms, Vs = _ekf_outputs(xlin, K, T, D, O, vs_diag, want_smoother)
     if nll is None:
         nll = torch.empty((K,), dtype=torch.float64, device=y.device)
     if change is None:

@@ -28,7 +28,7 @@ from typing import Literal
 import numpy as np
 
 from . import hip_ops
-from .posterior import _host_flags, _validate
+from ._problem import linear_problem, singlecam_problem, to_caller
 
 __all__ = ['process_noise_scale_from_times', 'smooth_time_varying', 'smooth_singlecam_irregular', 'MAX_SCALE']
 
@@ -84,20 +84,13 @@ def smooth_time_varying(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, proce
     at the true frame times.  With a decaying A it is only a process-noise scale: A itself is applied once per frame.
     s_finals usually comes from the drivers' search, which runs on the uniform model.  h_fn models are not
     supported."""
-    if h_fn is not None:
-        raise NotImplementedError('smooth_time_varying covers linear models; h_fn models are not supported')
-    K, T, O, D, s = _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, 1, None, 0, 0)
-    w = _check_scale(process_noise_scale, K, T)
-    flags = _host_flags(S0s, As, Cs, Qs)
-    from .core import _DeviceProblem, _to_host, _torch
-    torch = _torch()
-    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
-    ms, Vs = hip_ops.smooth_tv(P.y, P.var, torch.as_tensor(w, device=P.dev), *P.params,
-                               torch.as_tensor(s, device=P.dev), flags=P.flags, vs_diag=vs_diag)
-    if return_device:
-        return ms.transpose(0, 1), Vs.transpose(0, 1)
-    ms, Vs = _to_host(ms, Vs)
-    return np.swapaxes(ms, 0, 1), np.swapaxes(Vs, 0, 1)
+    L = linear_problem('smooth_time_varying', ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, h_fn)
+    w = _check_scale(process_noise_scale, L.K, L.T)
+    P, s_dev = L.upload()
+    from .core import _torch
+    ms, Vs = hip_ops.smooth_tv(P.y, P.var, _torch().as_tensor(w, device=P.dev), *P.params, s_dev, flags=P.flags,
+                               vs_diag=vs_diag)
+    return to_caller(return_device, (ms, Vs))
 
 
 def smooth_singlecam_irregular(marker_array, keypoint_names: list, s_finals, *, frame_times=None,
@@ -110,27 +103,14 @@ def smooth_singlecam_irregular(marker_array, keypoint_names: list, s_finals, *, 
         Vs (T, K, 2)   their posterior variances
     This driver's A is the identity, so with frame_times the model is Brownian motion sampled at the true times.
     s_finals: the smoothing parameters the driver returned - found by its search on the uniform model."""
-    from .core import ensemble
-    from .singlecam_smoother import initialize_kalman_filter
-    from .utils import center_predictions
     if (frame_times is None) == (process_noise_scale is None):
         raise ValueError('give exactly one of frame_times and process_noise_scale')
-    M, V, T, K, _ = marker_array.shape
-    if V != 1:
-        raise ValueError('smooth_singlecam_irregular takes a single-view marker array')
-    if len(keypoint_names) != K:
-        raise ValueError(f'{len(keypoint_names)} keypoint names for {K} keypoints')
     if frame_times is not None:
+        T = marker_array.shape[2]
         if np.shape(frame_times) != (T,):
             raise ValueError(f'frame_times must be {(T,)}; got {np.shape(frame_times)}')
         process_noise_scale = process_noise_scale_from_times(frame_times)
-    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)
-    _, centered, _, means = center_predictions(ens, quantile_keep_pca=100)
-    stats = np.asarray(ens.array)[0, 0]
-    cen = np.asarray(centered.array)[0, 0]
-    m0s, S0s, As, Qs, Cs = initialize_kalman_filter(centered)
-    ms, Vs = smooth_time_varying(np.swapaxes(cen, 0, 1), m0s, S0s, As, Cs, Qs, stats[:, :, 2:4], s_finals,
-                                 process_noise_scale, vs_diag=True)
-    mu = np.asarray(means.array)[0, 0, 0].astype(np.float32)                     # (K,2)
-    return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)) + mu[None],
+    model, _, mu = singlecam_problem('smooth_singlecam_irregular', marker_array, keypoint_names, avg_mode, var_mode)
+    ms, Vs = smooth_time_varying(*model, s_finals, process_noise_scale, vs_diag=True)
+    return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)) + mu.astype(np.float32)[None],
                 Vs=np.ascontiguousarray(np.swapaxes(Vs, 0, 1)))

@@ -31,8 +31,7 @@ from typing import Literal
 import numpy as np
 
 from . import hip_ops
-from .posterior import _host_flags, _validate
-from .robust import _check_counts
+from ._problem import check_iteration_counts, iterated_smooth, singlecam_problem
 
 __all__ = ['smooth_jumps', 'smooth_singlecam_jumps']
 
@@ -50,33 +49,8 @@ def smooth_jumps(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, nu: float
     arrays, or device tensors with return_device.  scales[k, t] is the process-noise scale of the step into frame t
     (entry 0 is 1 and unused): what smooth_time_varying takes as w.  change is max |u_new - u_old| over the keypoint's
     frames in the last update (0 when n_iters = 1).  h_fn models are not supported."""
-    if h_fn is not None:
-        raise NotImplementedError('smooth_jumps covers linear models; h_fn models are not supported')
-    nu, n_iters = _check_counts(nu, n_iters, tol, max_iters)
-    K, T, O, D, s = _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, 1, None, 0, 0)
-    flags = _host_flags(S0s, As, Cs, Qs)
-    from .core import _DeviceProblem, _to_host, _torch
-    torch = _torch()
-    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
-    s_dev = torch.as_tensor(s, device=P.dev)
-
-    def run(n, scales=None):
-        return hip_ops.smooth_jumps(P.y, P.var, *P.params, s_dev, nu=nu, n_iters=n, flags=P.flags, vs_diag=vs_diag,
-                                    scales=scales, scales_in=scales is not None)
-
-    ms, Vs, scales, change = run(n_iters)
-    if tol is not None:
-        # a continued block's first pass smooths again under the scales the previous block ended on, so a block of n
-        # passes adds n - 1 to `done`: the n_iters of the single call that gives the same bits
-        done = n_iters
-        while float(change.max()) >= tol and done < max_iters:
-            n = min(n_iters, int(max_iters) - done + 1)
-            ms, Vs, scales, change = run(n, scales)
-            done += n - 1
-    if return_device:
-        return ms.transpose(0, 1), Vs.transpose(0, 1), scales.transpose(0, 1), change
-    ms, Vs, scales, change = _to_host(ms, Vs, scales, change)
-    return np.swapaxes(ms, 0, 1), np.swapaxes(Vs, 0, 1), np.swapaxes(scales, 0, 1), change
+    return iterated_smooth('smooth_jumps', hip_ops.smooth_jumps, 'scales', (ys, m0s, S0s, As, Cs, Qs, ensemble_vars),
+                           s_finals, nu, n_iters, tol, max_iters, vs_diag, return_device, h_fn)
 
 
 def smooth_singlecam_jumps(marker_array, keypoint_names: list, s_finals, *, nu: float = 4.0, n_iters: int = 12, tol=None,
@@ -88,23 +62,10 @@ def smooth_singlecam_jumps(marker_array, keypoint_names: list, s_finals, *, nu: 
         Vs (T, K, 2)      their posterior variances
         scales (T, K)     the process-noise scale of the step into every frame, shared by x and y
     s_finals: the smoothing parameters the driver returned - found by its search on the Gaussian model."""
-    from .core import ensemble
-    from .singlecam_smoother import initialize_kalman_filter
-    from .utils import center_predictions
-    M, V, T, K, _ = marker_array.shape
-    if V != 1:
-        raise ValueError('smooth_singlecam_jumps takes a single-view marker array')
-    if len(keypoint_names) != K:
-        raise ValueError(f'{len(keypoint_names)} keypoint names for {K} keypoints')
-    _check_counts(nu, n_iters, tol, max_iters)
-    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)
-    _, centered, _, means = center_predictions(ens, quantile_keep_pca=100)
-    stats = np.asarray(ens.array)[0, 0]
-    cen = np.asarray(centered.array)[0, 0]
-    m0s, S0s, As, Qs, Cs = initialize_kalman_filter(centered)
-    ms, Vs, scales, _ = smooth_jumps(np.swapaxes(cen, 0, 1), m0s, S0s, As, Cs, Qs, stats[:, :, 2:4], s_finals, nu=nu,
-                                     n_iters=n_iters, tol=tol, max_iters=max_iters, vs_diag=True)
-    mu = np.asarray(means.array)[0, 0, 0].astype(np.float32)                     # (K,2)
-    return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)) + mu[None],
+    check_iteration_counts(nu, n_iters, tol, max_iters)
+    model, _, mu = singlecam_problem('smooth_singlecam_jumps', marker_array, keypoint_names, avg_mode, var_mode)
+    ms, Vs, scales, _ = smooth_jumps(*model, s_finals, nu=nu, n_iters=n_iters, tol=tol, max_iters=max_iters,
+                                     vs_diag=True)
+    return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)) + mu.astype(np.float32)[None],
                 Vs=np.ascontiguousarray(np.swapaxes(Vs, 0, 1)),
                 scales=np.ascontiguousarray(np.swapaxes(scales, 0, 1)))

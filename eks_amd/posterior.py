@@ -23,40 +23,11 @@ from typing import Literal
 import numpy as np
 
 from . import hip_ops
+from ._problem import linear_problem, singlecam_problem, to_caller
 
 __all__ = ['sample_kalman_posterior', 'sample_singlecam', 'smooth_increments', 'velocity_singlecam', 'SmoothIncrements']
 
 DEFAULT_MEMORY_BUDGET = 2 << 30     # bytes of device memory one group of draws (output + workspace) may take
-
-
-def _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, n_draws, h_fn, first_keypoint, first_draw):
-    if h_fn is not None:
-        raise NotImplementedError('posterior sampling covers linear models; h_fn models are not supported')
-    if int(n_draws) != n_draws or n_draws < 1:
-        raise ValueError('n_draws must be an integer >= 1')
-    if first_keypoint < 0 or first_draw < 0:
-        raise ValueError('first_keypoint and first_draw must be >= 0')
-    shp = tuple(np.shape(ys))
-    if len(shp) != 3:
-        raise ValueError(f'ys must be (K,T,O); got {shp}')
-    K, T, O = shp
-    if len(np.shape(m0s)) != 2 or np.shape(m0s)[0] != K:
-        raise ValueError(f'm0s must be (K,D); got {tuple(np.shape(m0s))}')
-    D = np.shape(m0s)[1]
-    for name, a, want in (('S0s', S0s, (K, D, D)), ('As', As, (K, D, D)), ('Cs', Cs, (K, O, D)), ('Qs', Qs, (K, D, D)),
-                          ('ensemble_vars', ensemble_vars, (T, K, O))):
-        if tuple(np.shape(a)) != want:
-            raise ValueError(f'{name} must be {want}; got {tuple(np.shape(a))}')
-    s = np.broadcast_to(np.asarray(s_finals, dtype=np.float64), (K,)) if np.ndim(s_finals) == 0 \
-        else np.asarray(s_finals, dtype=np.float64)
-    if s.shape != (K,):
-        raise ValueError(f's_finals must be a scalar or (K,); got {s.shape}')
-    return K, T, O, D, np.ascontiguousarray(s)
-
-
-def _host_flags(S0s, As, Cs, Qs) -> int:
-    from .core import _to_numpy
-    return hip_ops.model_flags(*(np.ascontiguousarray(_to_numpy(a, np.float64)) for a in (S0s, As, Cs, Qs)))
 
 
 def draws_per_group(K: int, T: int, D: int, O: int, flags: int, n_draws: int, memory_budget: int) -> int:
@@ -84,17 +55,18 @@ def sample_kalman_posterior(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, n
     those alone with first_keypoint = k0 / first_draw = d0.  Draws are produced in groups whose output and workspace
     fit `memory_budget` bytes of device memory, which changes no value.  noise (n_draws, T, K, W) float32 replaces
     the generator (W = D on diagonal models, D + O otherwise; zeros return the smoothed mean)."""
-    K, T, O, D, s = _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, n_draws, h_fn, first_keypoint,
-                              first_draw)
-    n_draws = int(n_draws)
-    flags = _host_flags(S0s, As, Cs, Qs)
+    L = linear_problem('sample_kalman_posterior', ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, h_fn)
+    if int(n_draws) != n_draws or n_draws < 1:
+        raise ValueError('n_draws must be an integer >= 1')
+    if first_keypoint < 0 or first_draw < 0:
+        raise ValueError('first_keypoint and first_draw must be >= 0')
+    K, T, O, D, flags, n_draws = L.K, L.T, L.O, L.D, L.flags, int(n_draws)
     W = hip_ops.sample_noise_width(D, O, flags)
     if noise is not None and tuple(np.shape(noise)) != (n_draws, T, K, W):
         raise ValueError(f'noise must be {(n_draws, T, K, W)}; got {tuple(np.shape(noise))}')
-    from .core import _DeviceProblem, _to_host, _torch
+    from .core import _to_host, _torch
     torch = _torch()
-    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
-    s_dev = torch.as_tensor(s, device=P.dev)
+    P, s_dev = L.upload()
     if noise is not None:
         noise = torch.as_tensor(noise, device=P.dev).to(torch.float32).contiguous()
     group = draws_per_group(K, T, D, O, flags, n_draws, memory_budget)
@@ -111,11 +83,8 @@ def sample_kalman_posterior(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, n
             ms = m
         if out_host is not None:
             out_host[d0:d1] = _to_host(dr)[0]
-    if return_device:
-        draws = out_dev.permute(2, 0, 1, 3)
-        return (draws, ms.transpose(0, 1)) if return_mean else draws
-    draws = np.transpose(out_host, (2, 0, 1, 3))
-    return (draws, np.swapaxes(_to_host(ms)[0], 0, 1)) if return_mean else draws
+    draws = out_dev.permute(2, 0, 1, 3) if return_device else np.transpose(out_host, (2, 0, 1, 3))
+    return (draws, *to_caller(return_device, (ms,))) if return_mean else draws
 
 
 def sample_singlecam(marker_array, keypoint_names: list, s_finals, n_draws: int, *, seed: int = 0,
@@ -126,23 +95,9 @@ def sample_singlecam(marker_array, keypoint_names: list, s_finals, n_draws: int,
     Rebuilds the ensemble, the centring and the prior as ensemble_kalman_smoother_singlecam does and adds the same
     means back: over many draws the mean approaches that driver's x, y columns and the variance its
     x_posterior_var, y_posterior_var columns.  s_finals: the smoothing parameters the driver returned."""
-    from .core import ensemble
-    from .singlecam_smoother import initialize_kalman_filter
-    from .utils import center_predictions
-    M, V, T, K, _ = marker_array.shape
-    if V != 1:
-        raise ValueError('sample_singlecam takes a single-view marker array')
-    if len(keypoint_names) != K:
-        raise ValueError(f'{len(keypoint_names)} keypoint names for {K} keypoints')
-    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)
-    _, centered, _, means = center_predictions(ens, quantile_keep_pca=100)
-    stats = np.asarray(ens.array)[0, 0]
-    cen = np.asarray(centered.array)[0, 0]
-    m0s, S0s, As, Qs, Cs = initialize_kalman_filter(centered)
-    draws = sample_kalman_posterior(np.swapaxes(cen, 0, 1), m0s, S0s, As, Cs, Qs, stats[:, :, 2:4], s_finals, n_draws,
-                                    seed=seed, memory_budget=memory_budget)
-    mu = np.asarray(means.array)[0, 0, 0].astype(np.float32)                     # (K,2)
-    return np.ascontiguousarray(np.transpose(draws, (1, 2, 0, 3))) + mu[None, None]
+    model, _, mu = singlecam_problem('sample_singlecam', marker_array, keypoint_names, avg_mode, var_mode)
+    draws = sample_kalman_posterior(*model, s_finals, n_draws, seed=seed, memory_budget=memory_budget)
+    return np.ascontiguousarray(np.transpose(draws, (1, 2, 0, 3))) + mu.astype(np.float32)[None, None]
 
 
 SmoothIncrements = namedtuple('SmoothIncrements', ['ms', 'Vs', 'lag1', 'dmean', 'dV'])
@@ -159,29 +114,22 @@ def smooth_increments(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, full
     all are views of the kernels' frame-major buffers, like run_kalman_smoother's.  dV is formed inside the
     backward pass as a sum of non-negative terms: Vs[t] + Vs[t+1] - 2 lag1[t] from the float32 outputs loses it to
     cancellation under heavy smoothing."""
-    K, T, O, D, s = _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, 1, h_fn, 0, 0)
-    flags = _host_flags(S0s, As, Cs, Qs)
+    L = linear_problem('smooth_increments', ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, h_fn)
     from . import _lib
-    from .core import _DeviceProblem, _to_host, _torch
-    torch = _torch()
-    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
+    from .core import _torch
+    P, s_dev = L.upload()
     diag_model = bool(P.flags & _lib.FLAG_DIAG_MODEL)
-    out = hip_ops.smooth_increments(P.y, P.var, *P.params, torch.as_tensor(s, device=P.dev), flags=P.flags,
-                                    vs_diag=diag_model or not full_cov)
+    out = hip_ops.smooth_increments(P.y, P.var, *P.params, s_dev, flags=P.flags, vs_diag=diag_model or not full_cov)
     names = SmoothIncrements._fields
-    if return_device:
-        res = {n: out[n] for n in names}
-        if diag_model and full_cov:                     # scalar chains: the matrices are the diagonal embedding
-            res.update({n: torch.diag_embed(res[n]) for n in ('Vs', 'lag1', 'dV')})
-        swap = lambda a: a.transpose(0, 1)
-    else:
-        res = dict(zip(names, _to_host(*(out[n] for n in names))))
-        if diag_model and full_cov:
-            eye = np.eye(D, dtype=np.float32)
-            res.update({n: res[n][..., :, None] * eye for n in ('Vs', 'lag1', 'dV')})
-        swap = lambda a: np.swapaxes(a, 0, 1)
-    return SmoothIncrements(swap(res['ms']), swap(res['Vs']), swap(res['lag1'])[:, :T - 1], swap(res['dmean'])[:, :T - 1],
-                            swap(res['dV'])[:, :T - 1])
+    embed = ('Vs', 'lag1', 'dV') if diag_model and full_cov else ()      # scalar chains: the matrices are the diagonal
+    if return_device:                                                   # embedding, made before the (K, T) view is taken
+        out.update({n: _torch().diag_embed(out[n]) for n in embed})
+    res = dict(zip(names, to_caller(return_device, [out[n] for n in names])))
+    if not return_device:
+        eye = np.eye(L.D, dtype=np.float32)
+        res.update({n: res[n][..., :, None] * eye for n in embed})
+    T = L.T
+    return SmoothIncrements(res['ms'], res['Vs'], res['lag1'][:, :T - 1], res['dmean'][:, :T - 1], res['dV'][:, :T - 1])
 
 
 def velocity_singlecam(marker_array, keypoint_names: list, s_finals, *, fps: float = 1.0,
@@ -194,22 +142,10 @@ def velocity_singlecam(marker_array, keypoint_names: list, s_finals, *, fps: flo
         velocity_var (T-1, K, 2)  Var(x_{t+1} - x_t | y) fps^2
         speed_rms    (T-1, K)     sqrt(E |v|^2) = fps sqrt(sum_d dmean^2 + dV): the exact root of the second moment
     s_finals: the smoothing parameters the driver returned."""
-    from .core import ensemble
-    from .singlecam_smoother import initialize_kalman_filter
-    from .utils import center_predictions
-    M, V, T, K, _ = marker_array.shape
-    if V != 1:
-        raise ValueError('velocity_singlecam takes a single-view marker array')
-    if len(keypoint_names) != K:
-        raise ValueError(f'{len(keypoint_names)} keypoint names for {K} keypoints')
     if not fps > 0:
         raise ValueError('fps must be positive')
-    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)
-    _, centered, _, _ = center_predictions(ens, quantile_keep_pca=100)
-    stats = np.asarray(ens.array)[0, 0]
-    cen = np.asarray(centered.array)[0, 0]
-    m0s, S0s, As, Qs, Cs = initialize_kalman_filter(centered)
-    inc = smooth_increments(np.swapaxes(cen, 0, 1), m0s, S0s, As, Cs, Qs, stats[:, :, 2:4], s_finals)
+    model, _, _ = singlecam_problem('velocity_singlecam', marker_array, keypoint_names, avg_mode, var_mode)
+    inc = smooth_increments(*model, s_finals)
     f = np.float32(fps)
     dmean = np.swapaxes(inc.dmean, 0, 1)                                        # (T-1, K, 2)
     dV = np.swapaxes(inc.dV, 0, 1)

@@ -27,25 +27,9 @@ from typing import Literal
 import numpy as np
 
 from . import hip_ops
-from .posterior import _host_flags, _validate
+from ._problem import check_iteration_counts, iterated_smooth, singlecam_problem
 
 __all__ = ['smooth_robust', 'smooth_singlecam_robust']
-
-
-def _check_counts(nu, n_iters, tol, max_iters):
-    nu = float(nu)
-    if not (np.isfinite(nu) and nu > 0):
-        raise ValueError('nu must be positive and finite')
-    if int(n_iters) != n_iters or n_iters < 1:
-        raise ValueError('n_iters must be an integer >= 1')
-    if tol is not None:
-        if not (np.isfinite(tol) and tol > 0):
-            raise ValueError('tol must be positive and finite')
-        if int(max_iters) != max_iters or max_iters < n_iters:
-            raise ValueError('max_iters must be an integer >= n_iters')
-        if n_iters < 2:
-            raise ValueError('tol needs n_iters >= 2: a single pass updates no weight')
-    return nu, int(n_iters)
 
 
 def smooth_robust(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, nu: float = 4.0, n_iters: int = 8, tol=None,
@@ -60,33 +44,8 @@ def smooth_robust(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, nu: floa
     Returns (ms (K,T,D), Vs (K,T,D,D) or its diagonal (K,T,D) with vs_diag, weights (K,T,O), change (K,)): float32
     NumPy arrays, or device tensors with return_device.  change is max |lam_new - lam_old| over the keypoint's frames
     and coordinates in the last weight update (0 when n_iters = 1).  h_fn models are not supported."""
-    if h_fn is not None:
-        raise NotImplementedError('smooth_robust covers linear models; h_fn models are not supported')
-    nu, n_iters = _check_counts(nu, n_iters, tol, max_iters)
-    K, T, O, D, s = _validate(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, 1, None, 0, 0)
-    flags = _host_flags(S0s, As, Cs, Qs)
-    from .core import _DeviceProblem, _to_host, _torch
-    torch = _torch()
-    P = _DeviceProblem(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, flags=flags)
-    s_dev = torch.as_tensor(s, device=P.dev)
-
-    def run(n, weights=None):
-        return hip_ops.smooth_robust(P.y, P.var, *P.params, s_dev, nu=nu, n_iters=n, flags=P.flags, vs_diag=vs_diag,
-                                     weights=weights, weights_in=weights is not None)
-
-    ms, Vs, weights, change = run(n_iters)
-    if tol is not None:
-        # a continued block's first pass smooths again under the weights the previous block ended on, so a block of n
-        # passes adds n - 1 to `done`: the n_iters of the single call that gives the same bits
-        done = n_iters
-        while float(change.max()) >= tol and done < max_iters:
-            n = min(n_iters, int(max_iters) - done + 1)
-            ms, Vs, weights, change = run(n, weights)
-            done += n - 1
-    if return_device:
-        return ms.transpose(0, 1), Vs.transpose(0, 1), weights.transpose(0, 1), change
-    ms, Vs, weights, change = _to_host(ms, Vs, weights, change)
-    return np.swapaxes(ms, 0, 1), np.swapaxes(Vs, 0, 1), np.swapaxes(weights, 0, 1), change
+    return iterated_smooth('smooth_robust', hip_ops.smooth_robust, 'weights', (ys, m0s, S0s, As, Cs, Qs, ensemble_vars),
+                           s_finals, nu, n_iters, tol, max_iters, vs_diag, return_device, h_fn)
 
 
 def smooth_singlecam_robust(marker_array, keypoint_names: list, s_finals, *, nu: float = 4.0, n_iters: int = 8, tol=None,
@@ -98,23 +57,10 @@ def smooth_singlecam_robust(marker_array, keypoint_names: list, s_finals, *, nu:
         Vs (T, K, 2)        their posterior variances
         weights (T, K, 2)   the weight of every observed coordinate, in (0, (nu + 1) / nu]
     s_finals: the smoothing parameters the driver returned - found by its search on the Gaussian model."""
-    from .core import ensemble
-    from .singlecam_smoother import initialize_kalman_filter
-    from .utils import center_predictions
-    M, V, T, K, _ = marker_array.shape
-    if V != 1:
-        raise ValueError('smooth_singlecam_robust takes a single-view marker array')
-    if len(keypoint_names) != K:
-        raise ValueError(f'{len(keypoint_names)} keypoint names for {K} keypoints')
-    _check_counts(nu, n_iters, tol, max_iters)
-    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)
-    _, centered, _, means = center_predictions(ens, quantile_keep_pca=100)
-    stats = np.asarray(ens.array)[0, 0]
-    cen = np.asarray(centered.array)[0, 0]
-    m0s, S0s, As, Qs, Cs = initialize_kalman_filter(centered)
-    ms, Vs, weights, _ = smooth_robust(np.swapaxes(cen, 0, 1), m0s, S0s, As, Cs, Qs, stats[:, :, 2:4], s_finals, nu=nu,
-                                       n_iters=n_iters, tol=tol, max_iters=max_iters, vs_diag=True)
-    mu = np.asarray(means.array)[0, 0, 0].astype(np.float32)                     # (K,2)
-    return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)) + mu[None],
+    check_iteration_counts(nu, n_iters, tol, max_iters)
+    model, _, mu = singlecam_problem('smooth_singlecam_robust', marker_array, keypoint_names, avg_mode, var_mode)
+    ms, Vs, weights, _ = smooth_robust(*model, s_finals, nu=nu, n_iters=n_iters, tol=tol, max_iters=max_iters,
+                                       vs_diag=True)
+    return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)) + mu.astype(np.float32)[None],
                 Vs=np.ascontiguousarray(np.swapaxes(Vs, 0, 1)),
                 weights=np.ascontiguousarray(np.swapaxes(weights, 0, 1)))

@@ -14,9 +14,10 @@ from typing import Literal
 import numpy as np
 import pandas as pd
 
-from .core import ensemble, run_kalman_smoother
+from ._problem import singlecam_problem
+from .core import run_kalman_smoother
 from .marker_array import MarkerArray, input_dfs_to_markerArray
-from .utils import center_predictions, format_data, make_dlc_pandas_index, write_prediction_csv
+from .utils import format_data, make_dlc_pandas_index, write_prediction_csv
 
 __all__ = ['fit_eks_singlecam', 'ensemble_kalman_smoother_singlecam']
 
@@ -63,18 +64,11 @@ def ensemble_kalman_smoother_singlecam(marker_array: MarkerArray, keypoint_names
             table, s_finals = out
             return pd.DataFrame(table.reshape(T, K * 9),
                                 columns=make_dlc_pandas_index(keypoint_names, labels=OUTPUT_LABELS)), s_finals
-    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)       # (1,1,T,K,5) float32
-    _, centered, _, means = center_predictions(ens, quantile_keep_pca=100)
-    stats = np.asarray(ens.array)[0, 0]                                       # (T,K,5)
-    cen = np.asarray(centered.array)[0, 0]                                    # (T,K,2)
-    m0s, S0s, As, Qs, Cs = initialize_kalman_filter(centered)
-    s_finals, ms, Vs = run_kalman_smoother(
-        ys=np.swapaxes(cen, 0, 1), m0s=m0s, S0s=S0s, As=As, Cs=Cs, Qs=Qs,
-        ensemble_vars=stats[:, :, 2:4], s_frames=s_frames, smooth_param=smooth_param,
-        blocks=blocks, vs_diag=True, **kalman_kwargs)
+    model, stats, mu = singlecam_problem(None, marker_array, keypoint_names, avg_mode, var_mode)
+    s_finals, ms, Vs = run_kalman_smoother(*model, s_frames=s_frames, smooth_param=smooth_param, blocks=blocks,
+                                           vs_diag=True, **kalman_kwargs)
     # C = I on this path: observation-space mean / variance are the state's
     # (reference :189-217 computes C m + mean and diag(C V C'))
-    mu = np.asarray(means.array)[0, 0, 0]                                     # (K,2)
     out = np.empty((T, K, 9))
     out[:, :, 0:2] = np.swapaxes(ms, 0, 1) + mu[None]
     out[:, :, 2] = stats[:, :, 4]
