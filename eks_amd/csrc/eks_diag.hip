@@ -44,6 +44,7 @@
 
 #include "eks_diag_lane.hpp"
 #include "eks_internal.hpp"
+#include "eks_win_walk.hpp"
 
 namespace eks {
 
@@ -319,13 +320,7 @@ struct BlockMap {
 //   G = 12, H = 2 (1 024 threads, 1.33 x the rows): the block's 16 waves cap the kernel at 128 VGPRs and it spills
 //                 (88-132 bytes of scratch per lane over the 18 forms): 260.2 -> 263.8 us, no gain;
 //   G =  8, H = 2 (  768 threads, 1.5 x the rows):  150-154 VGPRs, no scratch, one block per CU: 254.9 -> 233.5 us.
-// -DEKS_WIN_G=12 rebuilds the first for A/B.
-#ifndef EKS_WIN_G
-#define EKS_WIN_G 8
-#endif
-constexpr int kWinG = EKS_WIN_G;           // own chunks of a block
-constexpr int kWinH = 2;                   // halo chunks on either side (64 frames)
-constexpr int kWinW = kWinG + 2 * kWinH;   // waves of a block
+// -DEKS_WIN_G=12 rebuilds the first for A/B.  (kWinG, kWinH, kWinW: eks_win_walk.hpp.)
 constexpr float kWinTol = 0x1p-30f;
 constexpr int kWinDefault = 1;             // EKS_SMOOTH_WINDOW when unset
 // Shortest sequence that takes the windowed form (EKS_SMOOTH_WINDOW_MIN_T).  128 chains, scan-based -> windowed:
@@ -343,6 +338,7 @@ struct WinWs {
   int* gate;             // [tiles]   some lane of the tile needs the exact launches
   int nwg;               // window groups = ceil(nc / kWinG)
   int nan_bad;           // test mode: lanes that fail the check store NaN, nothing is recorded
+  int run_len;           // walk form: window groups per block (0: one block per window group)
 };
 
 // Row access of the fused kernels through buffer resources based at the first row of the wave's
@@ -641,10 +637,119 @@ __device__ __forceinline__ void replay_window_block(const BlockMap& L, const Dia
   }
 }
 
+// Walk form of the windowed replay: block = (64-chain tile, run of Wn.run_len consecutive window groups), one group per
+// step (eks_win_walk.hpp has the schedule).  The last two own chunks of a group are the next group's front halo and
+// its first two own chunks are the previous group's back halo, and a chunk's element does not depend on what enters
+// the chunk: every chunk is loaded and summarised once per run (plus the halos at the run's two ends) where the
+// block-per-group form asks for it 1.5 times.  Every group still enters from the stand-in belief pushed through its
+// own front halo and is checked against both halos: per lane the same operations in the same order as
+// replay_window_block, the same bits for every run length.  Nothing here waits for another block.
+template <int B, bool UNIT, int VS_ROW>
+__device__ __forceinline__ void replay_walk_block(const BlockMap& L, const DiagModel& M, const WinWs& Wn,
+                                                  const float* __restrict__ y, const float* __restrict__ var,
+                                                  float* __restrict__ ms, float* __restrict__ Vs) {
+  __shared__ float sh[5][kWalkRing][64];     // chunk elements, ring by chunk
+  __shared__ float shy[kWalkStand][64];      // the chains' observations on a front halo's first frame, ring by group
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int tile = L.tile0 + blockIdx.x % L.ntile;
+  const int run_len = Wn.run_len;
+  int run = blockIdx.x / L.ntile;
+  if (L.reverse) run = (Wn.nwg + run_len - 1) / run_len - 1 - run;
+  const int n = tile * 64 + lane;
+  constexpr int VW = VS_ROW == 0 ? 1 : VS_ROW;
+  const bool slow = n >= L.N || (Wn.slow != nullptr && Wn.slow[n] != 0);
+  if (__ballot(!slow) == 0) return;          // all 64 chains are the exact launches': no row is requested (block-uniform)
+  ChainParams<float> p{1.f, 1.f, 0.f};
+  float m0 = 0.f, P0 = 0.f;
+  if (n < L.N) {
+    p = load_chain_params(M, n);
+    load_chain_prior(M, n, m0, P0);
+  }
+  const int d = n % M.D;
+  float v0[B], v1[B];                        // the wave's chunk; a back-halo wave carries it into the next step
+  const int g0 = run * run_len, g1 = min(g0 + run_len, Wn.nwg);
+  for (int g = g0; g < g1; ++g) {            // block-uniform bounds: every wave reaches every barrier
+    const int base = walk_base(g);
+    const int off = walk_off(g, w);
+    const int j = base + off;
+    const bool valid = j >= 0 && j < L.nc;
+    const bool live = n < L.N && valid;      // lanes past N and chunks outside the sequence are masked
+    const int t0 = valid ? j * B : 0;
+    const int len = valid ? min(B, L.T - t0) : 0;
+    const bool full = len == B;
+    const size_t first = (size_t)t0 * L.N + (size_t)tile * 64;
+    if (walk_loads(off, g == g0)) {
+      Elem<float> own = elem_identity<float>();   // chunks outside the sequence compose as identities
+      float y0 = 0.f;
+      if (live) {
+        const BufferRows rows{rows_rsrc(y + first), rows_rsrc(var + first), (unsigned)lane * 4, (unsigned)L.N * 4};
+        if (full) {
+          load_rows<B, true>(rows, B, v0, v1);
+          y0 = v0[0];
+          own = summarize_loaded<B, UNIT, true>(v0, v1, B, p);
+        } else {
+          load_rows<B, false>(rows, len, v0, v1);
+          y0 = v0[0];
+          own = summarize_loaded<B, UNIT, false>(v0, v1, len, p);
+        }
+      }
+      const int slot = walk_elem_slot(j);
+      sh[0][slot][lane] = own.A; sh[1][slot][lane] = own.b; sh[2][slot][lane] = own.C; sh[3][slot][lane] = own.eta;
+      sh[4][slot][lane] = own.J;
+      // the row the next group's stand-in is made of, before this chunk's filter overwrites it
+      if (walk_saves_stand(j)) shy[walk_stand_slot(j)][lane] = y0;
+    }
+    __syncthreads();
+    if (!walk_replays(off) || !live) continue;
+    const int wo = off - kWinH;              // own chunk within the group
+    auto lds_elem = [&](int jj) {
+      const int q = walk_elem_slot(jj);
+      return Elem<float>{sh[0][q][lane], sh[1][q][lane], sh[2][q][lane], sh[3][q][lane], sh[4][q][lane]};
+    };
+    // a halo that reaches frame 0 starts from the chain's prior, one that reaches the last frame ends with no
+    // information: both exact, no check
+    const bool cut_front = base <= 0, cut_back = (g + 1) * kWinG + kWinH >= L.nc;
+    Elem<float> hf = lds_elem(base), hb = lds_elem(base + kWinH + kWinG);
+#pragma unroll
+    for (int q = 1; q < kWinH; ++q) {
+      hf = elem_combine(hf, lds_elem(base + q));
+      hb = elem_combine(hb, lds_elem(base + kWinH + kWinG + q));
+    }
+    float m = m0, P = P0;
+    if (!cut_front) {                        // stand-in: what the halo's first frame saw, variance S0
+      const float ys = shy[walk_stand_slot(base)][lane];
+      m = UNIT ? ys : ys * rcp(p.c);
+    }
+    // (comparisons written so that NaN fails)
+    const bool good = !slow && fabsf(m) <= 3e38f && (cut_front || fabsf(hf.A) <= kWinTol) &&
+                      (cut_back || fabsf(hb.A) <= kWinTol);
+    if (!good && !slow && wo == 0 && Wn.fail != nullptr) {
+      Wn.fail[(size_t)g * L.N + n] = 1;
+      atomicOr(&Wn.gate[tile], 1);
+    }
+    elem_apply(hf, m, P);
+    for (int q = 0; q < wo; ++q) elem_apply(lds_elem(base + kWinH + q), m, P);
+    if (full) filter_loaded<B, UNIT, true>(v0, v1, B, p, m, P);
+    else filter_loaded<B, UNIT, false>(v0, v1, len, p, m, P);
+    float eta = 0.f, J = 0.f;
+    elem_back(hb, eta, J);
+    for (int q = kWinG - 1; q > wo; --q) elem_back(lds_elem(base + kWinH + q), eta, J);
+    fuse_info(m, P, eta, J);
+    if (Wn.nan_bad && !good) m = P = __builtin_nanf("");
+    const BufferStore<VS_ROW> st{rows_rsrc(ms + first), rows_rsrc(Vs + first * VW), (unsigned)lane * 4,
+                                 (unsigned)L.N * 4, d};
+    if (good || Wn.nan_bad) {
+      if (full) smooth_rows<B, UNIT, true>(v0, v1, B, p, m, P, st);
+      else smooth_rows<B, UNIT, false>(v0, v1, len, p, m, P, st);
+    }
+  }
+}
+
 // K3 forms of the fused path
-constexpr int kFormElems = 0;      // chunk elements and per-group scan results from K1 / the group scan
+constexpr int kFormElems = 0;     // chunk elements and per-group scan results from K1 / the group scan
 constexpr int kFormRecompute = 1;  // the same, every chunk summarised again in K3
 constexpr int kFormWindow = 2;     // no K1, no scan: halo chunks instead
+constexpr int kFormWalk = 3;       // the same, a block walks a run of window groups
 
 // K3f: replay of chunk j = grp * kFW + w.  The belief entering the block and the information
 // leaving it come from the scan of the block aggregates; the wave pushes the former through the
@@ -653,10 +758,12 @@ constexpr int kFormWindow = 2;     // no K1, no scan: halo chunks instead
 // own 64 rows of y, var (holding both sets of elements in registers beside the chunk cost 180 VGPRs
 // and two thirds of the occupancy).
 template <int B, bool UNIT, int VS_ROW, int FORM>
-__global__ __launch_bounds__(FORM == kFormWindow ? 64 * kWinW : 64 * kFW) void diag_replay_blk_kernel(
+__global__ __launch_bounds__(FORM >= kFormWindow ? 64 * kWinW : 64 * kFW) void diag_replay_blk_kernel(
     BlockMap L, DiagModel M, DiagWs W, ScanWs S, WinWs Wn, const float* __restrict__ y, const float* __restrict__ var,
     float* __restrict__ ms, float* __restrict__ Vs) {
-  if constexpr (FORM == kFormWindow) {
+  if constexpr (FORM == kFormWalk) {
+    replay_walk_block<B, UNIT, VS_ROW>(L, M, Wn, y, var, ms, Vs);
+  } else if constexpr (FORM == kFormWindow) {
     replay_window_block<B, UNIT, VS_ROW>(L, M, Wn, y, var, ms, Vs);
   } else if constexpr (FORM == kFormRecompute) {
     replay_recompute_block<B, UNIT, VS_ROW, false>(L, M, S, Wn, y, var, ms, Vs);
@@ -926,6 +1033,37 @@ static void launch_replay(int vs_row, dim3 grid, hipStream_t st, const LaneMap& 
 #undef EKS_REPLAY
 }
 
+// Form of the windowed replay: the run length of the walk form, or 0 for one block per window group.
+// EKS_SMOOTH_WINDOW_WALK = 0 / 1 selects the form, EKS_SMOOTH_WINDOW_RUN = n forces the run length (tests, A/B); left
+// alone the length follows from the launch and the device's CU count (walk_run_length), and launches whose best run is
+// shorter than kWalkMinRun keep the block-per-group kernel: a run of one group is that kernel plus a loop.  The
+// outputs are the same bits either way.
+constexpr int kWalkDefault = 1;            // EKS_SMOOTH_WINDOW_WALK when unset
+constexpr int kWalkMinRun = 2;
+
+static int device_cu_count() {
+  static const int n = [] {                // queried once
+    int dev = 0, c = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
+      c = 256;
+    return c;
+  }();
+  return n;
+}
+
+static int walk_run(int ntile, int nwg) {
+  if (knob_int(KNOB_SMOOTH_WINDOW_WALK, kWalkDefault) == 0) return 0;
+  if (knob_set(KNOB_SMOOTH_WINDOW_RUN)) return min(max(knob_int(KNOB_SMOOTH_WINDOW_RUN, 1), 1), nwg);
+  thread_local int c_ntile = 0, c_nwg = 0, c_run = 0;   // a session repeats one shape
+  if (ntile != c_ntile || nwg != c_nwg) {
+    c_run = walk_run_length(ntile, nwg, device_cu_count());
+    c_ntile = ntile;
+    c_nwg = nwg;
+  }
+  return c_run >= kWalkMinRun ? c_run : 0;
+}
+
 int diag_smooth(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M,
                 float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st) {
   const int T = d.n_frames, D = d.state_dim, N = d.n_keypoints * D;
@@ -970,7 +1108,7 @@ int diag_smooth(const eks_dims_t& d, const float* y, const float* var, const Dia
   const int win_mode = knob_int(KNOB_SMOOTH_WINDOW, kWinDefault);
   const int win_min_t = max(kProbeLen, knob_int(KNOB_SMOOTH_WINDOW_MIN_T, kWinMinT));
   const bool windowed = fused && win_mode != 0 && T >= win_min_t;
-  WinWs Wn{nullptr, nullptr, nullptr, (L.nc + kWinG - 1) / kWinG, 0};
+  WinWs Wn{nullptr, nullptr, nullptr, (L.nc + kWinG - 1) / kWinG, 0, 0};
   if (windowed) {
     char* wb = base + 9 * pb + 9 * sb;
     if (win_mode == 2) {
@@ -1026,9 +1164,17 @@ int diag_smooth(const eks_dims_t& d, const float* y, const float* var, const Dia
 #define EKS_K3_WIN(UN, R)                                                                               \
   hipLaunchKernelGGL((diag_replay_blk_kernel<kChunk, UN, R, kFormWindow>), wgrid, dim3(64 * kWinW), 0,  \
                      st, Bw, M, W, S, Wn, y, var, ms, Vs)
+#define EKS_K3_WALK(UN, R)                                                                             \
+  hipLaunchKernelGGL((diag_replay_blk_kernel<kChunk, UN, R, kFormWalk>), wgrid, dim3(64 * kWinW), 0,    \
+                     st, Bw, M, W, S, Ww, y, var, ms, Vs)
 #define EKS_REPLAY_WIN(R)                                                                              \
   case R:                                                                                              \
-    if (unit)                                                                                          \
+    if (run_len > 0) {                                                                                 \
+      if (unit)                                                                                        \
+        EKS_K3_WALK(true, R);                                                                          \
+      else                                                                                             \
+        EKS_K3_WALK(false, R);                                                                         \
+    } else if (unit)                                                                                   \
       EKS_K3_WIN(true, R);                                                                             \
     else                                                                                               \
       EKS_K3_WIN(false, R);                                                                            \
@@ -1043,7 +1189,10 @@ int diag_smooth(const eks_dims_t& d, const float* y, const float* var, const Dia
         ProfScope ps("diag_replay", st);
         BlockMap Bw = Bm;
         Bw.reverse = k3_reverse;
-        const dim3 wgrid((unsigned)((long)Bw.ntile * Wn.nwg));
+        const int run_len = walk_run(Bw.ntile, Wn.nwg);   // 0: block per window group
+        WinWs Ww = Wn;
+        Ww.run_len = run_len;
+        const dim3 wgrid((unsigned)((long)Bw.ntile * (run_len > 0 ? (Wn.nwg + run_len - 1) / run_len : Wn.nwg)));
         switch (vs_row) {
           EKS_REPLAY_WIN(0)
           EKS_REPLAY_WIN(1)
@@ -1109,6 +1258,7 @@ int diag_smooth(const eks_dims_t& d, const float* y, const float* var, const Dia
 #undef EKS_REPLAY_BLK
 #undef EKS_REPLAY_WIN
 #undef EKS_K3_WIN
+#undef EKS_K3_WALK
 #undef EKS_K3_BLK
 #undef EKS_K1_BLK
     return hip_status(hipGetLastError());
