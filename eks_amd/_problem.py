@@ -1,6 +1,7 @@
 """What the feature functions that take the linear-Gaussian model (ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s) share:
 its validation, the way onto the device and back, the single-camera set-up, and the continuation loop of the two
-iterated smoothers.  Private: posterior, irregular, robust, jumps, em, diagnostics and the single-camera driver use it.
+iterated smoothers.  Private: posterior, irregular, robust, jumps, heavy_tails, em, diagnostics and the single-camera
+driver use it.
 torch and eks_amd.core are imported where a device is first needed, so every check here raises without one."""
 from __future__ import annotations
 

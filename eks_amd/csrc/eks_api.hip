@@ -20,7 +20,7 @@ static int check_dims(const eks_dims_t* d) {
   return EKS_OK;
 }
 
-// The model-taking entries (eks_smooth, _tv, _robust, _jumps, _increments, eks_em_stats, eks_innovations, eks_sample,
+// The model-taking entries (eks_smooth, _tv, _robust, _jumps, _heavy, _increments, eks_em_stats, eks_innovations, eks_sample,
 // eks_nll, eks_nll_argmin) share one tail, stated once here.  Each entry keeps its own shape check in front of it; the
 // ORDER of an entry's checks is part of its contract (tests/test_api_refusals_cpu.py pins every status).
 
@@ -167,6 +167,35 @@ int eks_smooth_jumps(const eks_dims_t* d, const float* y, const float* var, cons
   return smooth_iterated(d, {y, var, m0, S0, A, C, Q, s}, nu, n_iters, scales, scales_in, change, ms, Vs, workspace,
                          workspace_bytes, stream, eks_smooth_jumps_workspace_bytes, diag_smooth_jumps,
                          dense_smooth_jumps);
+}
+
+size_t eks_smooth_heavy_workspace_bytes(const eks_dims_t* d) {
+  return model_bytes(
+      d, smooth_tv_check(d), [d](int T, int) { return diag_smooth_heavy_workspace_bytes(T, d->n_keypoints, d->state_dim); },
+      dense_smooth_heavy_workspace_bytes);
+}
+
+// eks_smooth_jumps' order with two nu and two planes: shapes, either nu / n_iters, the model's pointers, the outputs
+// and a plane that is to be read, the workspace, its size
+int eks_smooth_heavy(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
+                     const double* A, const double* C, const double* Q, const double* s, double nu_obs, double nu_proc,
+                     int32_t n_iters, float* weights, float* scales, int32_t planes_in, float* change, float* ms,
+                     float* Vs, void* workspace, size_t workspace_bytes, eks_stream_t stream) {
+  const int rc = smooth_tv_check(d);
+  if (rc != EKS_OK) return rc;
+  if (!(nu_obs > 0.0) || !(nu_obs <= 1.7e308) || !(nu_proc > 0.0) || !(nu_proc <= 1.7e308) || n_iters < 1)
+    return EKS_ERR_SHAPE;
+  const bool plane_missing = ((planes_in & 1) && !weights) || ((planes_in & 2) && !scales);
+  auto run = [&](auto kernels, const auto& M) {
+    return kernels(*d, y, var, M, nu_obs, nu_proc, n_iters, weights, scales, planes_in, change, ms, Vs, workspace,
+                   workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  };
+  return model_call(
+      d, {y, var, m0, S0, A, C, Q, s},
+      !ms || !Vs || plane_missing ? EKS_ERR_NULL
+                                  : workspace_status(workspace, workspace_bytes, eks_smooth_heavy_workspace_bytes(d)),
+      [&](const DiagModel& M) { return run(diag_smooth_heavy, M); },
+      [&](const DenseModel& M) { return run(dense_smooth_heavy, M); });
 }
 
 // shapes eks_smooth_increments takes (EKS_OK) or the status it refuses them with; nothing here touches the device

@@ -10,8 +10,8 @@
 //   D3 dense_replay    : lane = (keypoint, chunk): exact filter, fuse, RTS; filtered beliefs go
 //                        through a per-lane scratch record stream (these problems are tiny:
 //                        BASELINE config 4 is 4 keypoints x 50k frames, latency- not HBM-bound)
-// Six more features run D1 -> D2 -> a replay kernel of their own on this organisation (increments, tv, robust, jumps,
-// EM statistics, innovations).  Their host side is written once: checks, layout and tail (DensePass, dense_pass_begin,
+// Seven more features run D1 -> D2 -> a replay kernel of their own on this organisation (increments, tv, robust, jumps,
+// heavy, EM statistics, innovations).  Their host side is written once: checks, layout and tail (DensePass, dense_pass_begin,
 // dense_generic_workspace_bytes) and the launches (dense_prelude, dense_tv_prelude, dense_pass_launch).  The kernels'
 // opening lines are not shared, on measurement: DESIGN.md 9k.
 // The losses of this path (eks_nll, eks_ar1_nll) live in eks_loss_kernels.hpp.
@@ -24,6 +24,7 @@
 #include "eks_increments_lane.hpp"
 #include "eks_innov_lane.hpp"
 #include "eks_internal.hpp"
+#include "eks_smooth_heavy_lane.hpp"
 #include "eks_smooth_jumps_lane.hpp"
 #include "eks_smooth_robust_lane.hpp"
 #include "eks_smooth_tv_lane.hpp"
@@ -720,6 +721,113 @@ int dense_smooth_jumps(const eks_dims_t& d, const float* y, const float* var, co
     }
   })
   return dense_smooth_tv(d, y, var, plane, 1, Mm, ms, Vs, ws, ws_bytes, st);
+}
+
+// ---- eks_smooth_heavy: n_iters passes under r / lam AND the scale plane ---------------------------------------------
+// dense_tv_summarize_kernel on RobustObs, the scan, a replay (eks_smooth_heavy_lane.hpp) that updates the weights in
+// place and writes delta_t into a [T][K] float64 plane, and the combine launch; the last pass writes ms, Vs under both
+// planes.  Tail: the [T][K][O] float weight plane and the [T][K] float scale plane (each used when the caller passes
+// none), then the delta plane.
+template <int D>
+__global__ __launch_bounds__(64) void dense_heavy_summarize_kernel(DenseGeom G, DenseModelPtrs M,
+                                                                  const double* __restrict__ s, RobustObs<D> obs,
+                                                                  const float* __restrict__ scales,
+                                                                  double* __restrict__ elems,
+                                                                  double* __restrict__ first) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.ncs) return;
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  const DenseNoiseScale ns{scales, G.K, k};
+  const int t0 = j * G.Bs, len = min(G.Bs, G.T - t0);
+  const DElem<double, D> e = dense_tv_element<D>(obs, ns, k, t0, len, F, sQ, fid);
+  store_delem<double, D>(elems + (size_t)idx * delem_doubles<D>(), e);
+  if (j == 0) {   // the belief the scan starts from: the prior updated with frame 0 (no predict, no w)
+    Vec<double, D> m;
+    Mat<double, D> P;
+    load_prior<D>(M, k, m, P);
+    belief_update_obs<D>(obs, k, 0, nullptr, m, P);
+    dense_store_rec<D>(first + (size_t)k * (D + D * D), 1, m, P);
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(64) void dense_heavy_replay_kernel(DenseGeom G, DenseModelPtrs M,
+                                                               const double* __restrict__ s, RobustObs<D> obs,
+                                                               const float* scales, float* lam, double nu, int last,
+                                                               float* change, const double* __restrict__ pre,
+                                                               const double* __restrict__ suf,
+                                                               const double* __restrict__ bprior,
+                                                               const double* __restrict__ bsuffix,
+                                                               double* __restrict__ filt, double* __restrict__ delta,
+                                                               float* __restrict__ ms, float* __restrict__ Vs,
+                                                               int vs_diag) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.nc) return;
+  constexpr int REC = D + D * D;
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  const DenseNoiseScale ns{scales, G.K, k};
+  Vec<double, D> m, eta;
+  Mat<double, D> P, J;
+  dense_chunk_boundary<D>(G, M, k, j, j, pre, suf, bprior, bsuffix, m, P, eta, J);   // one element per lane (Bs == B)
+  const int t0 = j * G.B, len = min(G.B, G.T - t0);
+  const double ch = dense_heavy_replay_chunk<D>(obs, ns, lam, nu, last != 0, k, t0, len, F, sQ, fid, m, P, eta, J,
+                                                filt + (size_t)t0 * REC * G.K + k, delta, ms, Vs, vs_diag != 0,
+                                                (size_t)G.K);
+  if (change && !last) robust_change_max(change + k, (float)ch);
+}
+
+static size_t dense_heavy_tail_bytes(int T, int K, int O) {
+  return dense_robust_tail_bytes(T, K, O) + dense_jumps_tail_bytes(T, K);
+}
+size_t dense_smooth_heavy_workspace_bytes(int T, int K, int D, int O) {
+  return dense_generic_workspace_bytes(T, K, D, O, T, dense_heavy_tail_bytes(T, K, O));
+}
+
+int dense_smooth_heavy(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu_obs,
+                       double nu_proc, int n_iters, float* weights, float* scales, int planes_in, float* change,
+                       float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, O = d.obs_dim;
+  DensePass P;
+  int rc = dense_pass_begin(d, Mm, T, dense_heavy_tail_bytes(T, K, O), ws, ws_bytes, P);
+  if (rc != EKS_OK) return rc;
+  char* tail = P.tail;
+  float* lam = weights ? weights : reinterpret_cast<float*>(tail);
+  tail += dense_robust_tail_bytes(T, K, O);
+  float* plane = scales ? scales : reinterpret_cast<float*>(tail);
+  double* delta = reinterpret_cast<double*>(tail + dense_jumps_scale_bytes(T, K));
+  rc = jumps_init_plane(plane, T, K, planes_in & 2, nullptr, st);
+  if (rc != EKS_OK) return rc;
+  if (change) {
+    const hipError_t e = hipMemsetAsync(change, 0, 2 * (size_t)K * sizeof(float), st);
+    if (e != hipSuccess) return hip_status(e);
+  }
+  const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
+  EKS_DISPATCH_D(d.state_dim, {
+    for (int it = 0; it < n_iters; ++it) {
+      const int last = it == n_iters - 1;
+      float* ch = it == n_iters - 2 ? change : nullptr;
+      const RobustObs<DD> obs = make_robust_obs<DD>(y, var, (it > 0 || (planes_in & 1)) ? lam : nullptr, K, O, P.M);
+      dense_pass_launch(P, "dense_heavy_summarize", st, dense_heavy_summarize_kernel<DD>, obs, plane, P.L.elems,
+                        P.L.first);
+      {
+        ProfScope ps("dense_heavy_scan", st);
+        dense_scan_launch<DD>(P.G, P.L, kGateOpen, st);
+      }
+      dense_pass_launch(P, "dense_heavy_replay", st, dense_heavy_replay_kernel<DD>, obs, plane, lam, nu_obs, last, ch,
+                        P.L.pre, P.L.suf, P.L.bprior, P.L.bsuffix, P.L.filt, delta, ms, Vs, vs_diag);
+      if (!last) {
+        rc = jumps_combine(delta, true, 1, plane, ch ? ch + K : nullptr, T, K, nu_proc, DD, st);
+        if (rc != EKS_OK) return rc;
+      }
+    }
+  })
+  return hip_status(hipGetLastError());
 }
 
 // ---- eks_em_stats: dense_increments' organisation with the outputs replaced by a sum --------------------------------

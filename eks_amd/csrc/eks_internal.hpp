@@ -182,6 +182,17 @@ int dense_smooth_jumps(const eks_dims_t& d, const float* y, const float* var, co
 int jumps_init_plane(float* plane, int T, int K, int scales_in, float* change, hipStream_t st);
 int jumps_combine(const void* contrib, bool f64, int nd, float* scales, float* change, int T, int K, double nu, int D,
                   hipStream_t st);
+// the smoother under Student-t noise on both sides (eks_smooth_heavy.hip: scalar chains, eks_smooth_tv's shapes on
+// eks_em_stats' workspace plus a weight, a scale and a contribution plane; eks_dense.hip: general models, always the
+// generic kernels).  change: [2][K], row 0 the weights', row 1 the scales'
+size_t diag_smooth_heavy_workspace_bytes(int T, int K, int D);
+int diag_smooth_heavy(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double nu_obs,
+                      double nu_proc, int n_iters, float* weights, float* scales, int planes_in, float* change,
+                      float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);
+size_t dense_smooth_heavy_workspace_bytes(int T, int K, int D, int O);
+int dense_smooth_heavy(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double nu_obs,
+                       double nu_proc, int n_iters, float* weights, float* scales, int planes_in, float* change,
+                       float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M,
                  float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);

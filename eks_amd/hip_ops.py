@@ -295,6 +295,40 @@ def smooth_jumps(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 12,
                             vs_diag, scales, scales_in, want_change)
 
 
+def smooth_heavy(y, var, m0, S0, A, C, Q, s, nu_obs: float = 4.0, nu_proc: float = 4.0, n_iters: int = 12, flags: int = 0,
+                 vs_diag: bool = False, weights=None, scales=None, planes_in: int = 0, want_change: bool = True):
+    """eks_smooth_heavy: eks_smooth under Student-t noise on observations (`nu_obs`, one weight per scalar observation)
+    and process (`nu_proc`, one scale per frame and keypoint) at once, `n_iters` smoothing passes enqueued back to back
+    (include/eks_hip.h has the model).  `weights` (T, K, O) and `scales` (T, K): float32 device tensors that receive
+    the planes; planes_in bit 0 / bit 1: the first pass starts from the contents of weights / scales.  Returns
+    (ms, Vs, weights, scales, change): change is (2, K) float32, row 0 the largest weight change and row 1 the largest
+    change of u = 1 / scale in the last update (None without want_change)."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
+    dev = bufs[0].device
+    planes_in = int(planes_in)
+    if planes_in & ~3:
+        raise ValueError('planes_in is a mask of bit 0 (weights) and bit 1 (scales)')
+    planes = []
+    for bit, name, plane, shape in ((1, 'weights', weights, (T, K, O)), (2, 'scales', scales, (T, K))):
+        if planes_in & bit and plane is None:
+            raise ValueError(f'planes_in bit {bit >> 1} needs a {name} tensor')
+        if plane is None:
+            plane = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif not plane.is_contiguous():
+            raise ValueError(f'{name} must be contiguous: it is written in place')
+        planes.append(_chk(plane, torch.float32, name, shape))
+    dims = _dims(K, T, D, O, _vs_flags(flags, vs_diag))
+    ms, Vs = _ms_Vs(T, K, D, vs_diag, dev)
+    change = torch.empty((2, K), dtype=torch.float32, device=dev) if want_change else None
+    ws = _workspace(lib.eks_smooth_heavy_workspace_bytes(ctypes.byref(dims)), dev)
+    rc = lib.eks_smooth_heavy(ctypes.byref(dims), *[_ptr(b) for b in bufs], float(nu_obs), float(nu_proc), int(n_iters),
+                              _ptr(planes[0]), _ptr(planes[1]), planes_in, _ptr(change), _ptr(ms), _ptr(Vs), _ptr(ws),
+                              ws.numel(), _stream())
+    _lib.check(rc, 'eks_smooth_heavy')
+    return ms, Vs, planes[0], planes[1], change
+
+
 def smooth_increments(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False,
                       want=('lag1', 'dmean', 'dV'), want_smooth: bool = True):
     """eks_smooth_increments: eks_smooth plus lag1 = Cov(x_t, x_{t+1} | y), dmean = E[x_{t+1} - x_t | y] and

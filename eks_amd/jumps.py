@@ -21,8 +21,9 @@ A scale near 1 (at most a few) says the frame moved like the rest of the session
 marks a jump INTO that frame.  The returned scales are exactly what smooth_time_varying takes as `w`.
 
 What it is not: nu is not fitted; s_finals comes from the drivers' search on the Gaussian model (there is no search
-under this model); the scales do not combine with eks_amd.robust's observation weights, a caller's own frame-interval
-scale, the sampler, increments, EM or innovations.
+under this model); the scales do not combine with a caller's own frame-interval scale, the sampler, increments, EM
+or innovations.  With eks_amd.robust's observation weights they combine in
+eks_amd.heavy_tails: a session with wrong observations AND fast movements wants that model.
 """
 from __future__ import annotations
 

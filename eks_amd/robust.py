@@ -16,8 +16,8 @@ residual of the frame.  The passes run on the device without a host round trip. 
     smooth_singlecam_robust(marker_array, keypoint_names, s_finals, nu=4.0, n_iters=8, ...) -> dict(ms, Vs, weights)
 
 What it is not: nu is not fitted; s_finals comes from the drivers' search on the Gaussian model (there is no search
-under the robust model); the weights do not combine with a process-noise scale, the sampler, increments, EM or
-innovations; one weight per coordinate, not per keypoint.  A weight near (nu + 1) / nu says the frame agrees with its
+under the robust model); the weights do not combine with a caller's process-noise scale, the sampler, increments, EM or
+innovations (with the Student-t scales of eks_amd.jumps they combine in eks_amd.heavy_tails); one weight per coordinate, not per keypoint.  A weight near (nu + 1) / nu says the frame agrees with its
 neighbours, a weight near 0 that it was discounted as an outlier.
 """
 from __future__ import annotations

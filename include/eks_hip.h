@@ -184,6 +184,46 @@ int eks_smooth_jumps(const eks_dims_t* dims, const float* y, const float* var, c
                      float* scales, int32_t scales_in, float* change, float* ms, float* Vs, void* workspace,
                      size_t workspace_bytes, eks_stream_t stream);
 
+/* ---- eks_smooth under Student-t noise on BOTH sides: eks_smooth_robust's weight per scalar observation AND
+ * eks_smooth_jumps' scale per keypoint and frame, for sessions that hold wrong observations and true fast movements
+ * at once (alone, the robust model reads a reach as a run of outliers and the jumps model follows a one-frame swap as
+ * two jumps).  No reference counterpart.
+ *     y_t | x_t, lam_t ~ N(C x_t, r_t / lam_t),   lam_t ~ Gamma(nu_obs / 2, rate nu_obs / 2),   r_t = clip_var(var_t),
+ *     eps_t | u_t ~ N(0, s Q / u_t),              u_t ~ Gamma(nu_proc / 2, rate nu_proc / 2),   t = 1 .. T-1,
+ * by mean field over q(x) q(lam) q(u).  A call runs n_iters >= 1 smoothing passes, all enqueued back to back.  Every
+ * pass smooths under r_eff = clip_var(r / lam) and w = 1 / u; every pass but the last then sets, from that one
+ * smoothed posterior, lam = (nu_obs + 1) / (nu_obs + delta_obs) and w = (nu_proc + delta_proc) / (nu_proc + D) with
+ * eks_smooth_robust's and eks_smooth_jumps' delta, clamps and floors.  Given q(x) the two updates are independent, so
+ * the variational bound cannot drop.  The last pass writes ms, Vs and updates nothing: the planes returned are the
+ * ones the outputs were smoothed under.  n_iters = 1 without input planes is the Gaussian smoother.
+ * dims, flags, y, var, the parameters and the layouts of ms and Vs are exactly those of eks_smooth_tv.
+ *   nu_obs, nu_proc  degrees of freedom of the two sides, each finite and > 0.
+ *   weights     float32 [T][K][O] as eks_smooth_robust's; may be NULL (a plane of the workspace serves).
+ *   scales      float32 [T][K] as eks_smooth_jumps'; may be NULL (a plane of the workspace serves).  Row 0 is never
+ *               read and is returned as 1.  The size query always includes both planes.
+ *   planes_in   bit 0: the first pass starts from the caller's weights; bit 1: from the caller's scales (each value
+ *               finite and > 0).  A bit set with a NULL plane gives EKS_ERR_NULL.
+ *   change      float32 [2][K], may be NULL: row 0 max |lam_new - lam_old|, row 1 max |u_new - u_old| (u = 1 / w) of
+ *               the call's last update.  The call zeroes it first; it stays zero when n_iters = 1.
+ *   continuing  n1 passes continued through both planes (planes_in = 3) by n2 passes are one call of n1 + n2 - 1
+ *               passes, bit for bit.
+ *   scalar chains   float32 lanes.  A middle pass is six launches: a summarize under both planes, eks_em_stats'
+ *               three-launch scan, a replay without outputs - one backward loop that stores every chain's
+ *               delta_{t,d} into a [T][K D] plane and the new weights in place - and eks_smooth_jumps' combine launch,
+ *               the only one that changes the scales.  The last pass is five launches.  Workspace: eks_em_stats' plus
+ *               the three planes.  Never the windowed replay.
+ *   general models  D <= 6 and O <= 64 (else EKS_ERR_UNSUPPORTED and a workspace size of 0); always the generic
+ *               float64 summarize / scan / replay kernels, the same combine launch.  Correct, not tuned.
+ *   accuracy    the limits of eks_smooth_robust's weights and eks_smooth_jumps' scales both apply.
+ * Refusals are eks_smooth_jumps', in the same order, with EKS_ERR_SHAPE when either nu is non-finite or non-positive
+ * or n_iters < 1; all are returned before anything is enqueued and leave every output untouched.  The size query
+ * returns 0 for refused shapes. ------------------ */
+size_t eks_smooth_heavy_workspace_bytes(const eks_dims_t* dims);
+int eks_smooth_heavy(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,
+                     const double* A, const double* C, const double* Q, const double* s, double nu_obs, double nu_proc,
+                     int32_t n_iters, float* weights, float* scales, int32_t planes_in, float* change, float* ms,
+                     float* Vs, void* workspace, size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- joint posterior trajectories: n_draws draws of x_1..x_T from the smoothing distribution p(x | y) of the model
  * eks_smooth smooths (same dims, flags, y, var and parameters; EKS_FLAG_VS_DIAG is ignored).  No reference counterpart:
  * the reference returns the per-frame marginals ms, Vs only (eks/core.py:296-297), which say nothing about how the
