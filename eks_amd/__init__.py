@@ -27,6 +27,8 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'process_noise_scale_from_times': 'irregular', 'smooth_time_varying': 'irregular',
         'smooth_singlecam_irregular': 'irregular',
         'smooth_robust': 'robust', 'smooth_singlecam_robust': 'robust',
+        'smooth_robust_grouped': 'robust', 'smooth_singlecam_robust_grouped': 'robust',
+        'smooth_multicam_robust': 'robust',
         'smooth_jumps': 'jumps', 'smooth_singlecam_jumps': 'jumps',
         'smooth_heavy_tailed': 'heavy_tails', 'smooth_singlecam_heavy_tailed': 'heavy_tails',
     }

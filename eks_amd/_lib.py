@@ -38,6 +38,9 @@ SIGNATURES = {
     'eks_smooth_robust_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
     'eks_smooth_robust': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 8 + [c_double, c_int32, c_void_p, c_int32]
                           + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    'eks_smooth_robust_group_workspace_bytes': (c_size_t, [POINTER(EksDims), c_int32]),
+    'eks_smooth_robust_group': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 8
+                                + [c_double, c_int32, c_int32, c_void_p, c_int32] + [c_void_p] * 4 + [c_size_t, c_void_p]),
     'eks_smooth_jumps_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
     'eks_smooth_jumps': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 8 + [c_double, c_int32, c_void_p, c_int32]
                          + [c_void_p] * 4 + [c_size_t, c_void_p]),

@@ -20,7 +20,7 @@ static int check_dims(const eks_dims_t* d) {
   return EKS_OK;
 }
 
-// The model-taking entries (eks_smooth, _tv, _robust, _jumps, _heavy, _increments, eks_em_stats, eks_innovations, eks_sample,
+// The model-taking entries (eks_smooth, _tv, _robust, _robust_group, _jumps, _heavy, _increments, eks_em_stats, eks_innovations, eks_sample,
 // eks_nll, eks_nll_argmin) share one tail, stated once here.  Each entry keeps its own shape check in front of it; the
 // ORDER of an entry's checks is part of its contract (tests/test_api_refusals_cpu.py pins every status).
 
@@ -64,13 +64,13 @@ static int smooth_tv_check(const eks_dims_t* d) {
   return dense_smooth_tv_workspace_bytes(d->n_frames, d->n_keypoints, d->state_dim, d->obs_dim) ? EKS_OK : EKS_ERR_SHAPE;
 }
 
-// eks_smooth_robust and eks_smooth_jumps: one entry around two pairs of kernels whose signatures agree; `plane` is the
+// eks_smooth_robust, eks_smooth_robust_group and eks_smooth_jumps: one entry around two pairs of kernels whose signatures agree; `plane` is the
 // weights of the one and the scales of the other, `need` the entry's workspace query.  Order: eks_smooth_tv's shapes and
 // refusals, nu / n_iters, the model's pointers, the outputs and a plane that is to be read, the workspace, its size.
-template <class Diag, class Dense>
+template <class Need, class Diag, class Dense>
 static int smooth_iterated(const eks_dims_t* d, const ModelArgs& a, double nu, int32_t n_iters, float* plane,
                            int32_t plane_in, float* change, float* ms, float* Vs, void* workspace, size_t workspace_bytes,
-                           eks_stream_t stream, size_t need(const eks_dims_t*), Diag diag, Dense dense) {
+                           eks_stream_t stream, Need need, Diag diag, Dense dense) {
   const int rc = smooth_tv_check(d);
   if (rc != EKS_OK) return rc;
   if (!(nu > 0.0) || !(nu <= 1.7e308) || n_iters < 1) return EKS_ERR_SHAPE;
@@ -167,6 +167,43 @@ int eks_smooth_jumps(const eks_dims_t* d, const float* y, const float* var, cons
   return smooth_iterated(d, {y, var, m0, S0, A, C, Q, s}, nu, n_iters, scales, scales_in, change, ms, Vs, workspace,
                          workspace_bytes, stream, eks_smooth_jumps_workspace_bytes, diag_smooth_jumps,
                          dense_smooth_jumps);
+}
+
+// eks_smooth_robust's shapes, then the group: at least 1 and a divisor of O
+static int robust_group_check(const eks_dims_t* d, int32_t group) {
+  const int rc = smooth_tv_check(d);
+  if (rc != EKS_OK) return rc;
+  return group < 1 || d->obs_dim % group != 0 ? EKS_ERR_SHAPE : EKS_OK;
+}
+
+size_t eks_smooth_robust_group_workspace_bytes(const eks_dims_t* d, int32_t group) {
+  if (robust_group_check(d, group) == EKS_OK && group == 1) return eks_smooth_robust_workspace_bytes(d);
+  return model_bytes(
+      d, robust_group_check(d, group), [group](int T, int N) { return diag_smooth_robust_group_workspace_bytes(T, N, group); },
+      [group](int T, int K, int D, int O) { return dense_smooth_robust_group_workspace_bytes(T, K, D, O, group); });
+}
+
+// eks_smooth_robust's order with the group's check behind the shapes; group = 1 IS eks_smooth_robust
+int eks_smooth_robust_group(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
+                            const double* A, const double* C, const double* Q, const double* s, double nu, int32_t group,
+                            int32_t n_iters, float* weights, int32_t weights_in, float* change, float* ms, float* Vs,
+                            void* workspace, size_t workspace_bytes, eks_stream_t stream) {
+  const int rc = robust_group_check(d, group);
+  if (rc != EKS_OK) return rc;
+  if (group == 1)
+    return eks_smooth_robust(d, y, var, m0, S0, A, C, Q, s, nu, n_iters, weights, weights_in, change, ms, Vs, workspace,
+                             workspace_bytes, stream);
+  return smooth_iterated(
+      d, {y, var, m0, S0, A, C, Q, s}, nu, n_iters, weights, weights_in, change, ms, Vs, workspace, workspace_bytes,
+      stream, [group](const eks_dims_t* dd) { return eks_smooth_robust_group_workspace_bytes(dd, group); },
+      [group](const eks_dims_t& dd, const float* yy, const float* vv, const DiagModel& M, double nu_, int n, float* w,
+              int w_in, float* ch, float* ms_, float* Vs_, void* ws, size_t wsb, hipStream_t st) {
+        return diag_smooth_robust_group(dd, yy, vv, M, nu_, group, n, w, w_in, ch, ms_, Vs_, ws, wsb, st);
+      },
+      [group](const eks_dims_t& dd, const float* yy, const float* vv, const DenseModel& M, double nu_, int n, float* w,
+              int w_in, float* ch, float* ms_, float* Vs_, void* ws, size_t wsb, hipStream_t st) {
+        return dense_smooth_robust_group(dd, yy, vv, M, nu_, group, n, w, w_in, ch, ms_, Vs_, ws, wsb, st);
+      });
 }
 
 size_t eks_smooth_heavy_workspace_bytes(const eks_dims_t* d) {

@@ -26,6 +26,7 @@
 #include "eks_internal.hpp"
 #include "eks_smooth_heavy_lane.hpp"
 #include "eks_smooth_jumps_lane.hpp"
+#include "eks_smooth_robust_group_lane.hpp"
 #include "eks_smooth_robust_lane.hpp"
 #include "eks_smooth_tv_lane.hpp"
 
@@ -654,6 +655,70 @@ int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, c
       const RobustObs<DD> obs = make_robust_obs<DD>(y, var, (it > 0 || weights_in) ? lam : nullptr, K, O, P.M);
       dense_prelude<DD>(P.G, P.M, P.s, obs, P.L, kGateOpen, "dense_robust_summarize", "dense_robust_scan", st);
       dense_pass_launch(P, "dense_robust_replay", st, dense_robust_replay_kernel<DD>, obs, lam, nu, last,
+                        it == n_iters - 2 ? change : nullptr, P.L.pre, P.L.suf, P.L.bprior, P.L.bsuffix, P.L.filt, ms,
+                        Vs, vs_diag);
+    }
+  })
+  return hip_status(hipGetLastError());
+}
+
+// ---- eks_smooth_robust_group: dense_smooth_robust with one weight per group of g coordinates -------------------------
+// The observation source reads lam[t][k][o / g] (eks_smooth_robust_group_lane.hpp: RobustGroupObs); the replay's emit
+// step holds every delta_o of its keypoint and frame, sums them per group and writes lam[t][k][G] in place: no combine
+// launch.  Tail: one [T][K][O / g] float plane of weights, used when the caller passes none.
+template <int D>
+__global__ __launch_bounds__(64) void dense_robust_group_replay_kernel(DenseGeom G, DenseModelPtrs M,
+                                                                      const double* __restrict__ s,
+                                                                      RobustGroupObs<D> obs, float* lam, double nu,
+                                                                      int last, float* change,
+                                                                      const double* __restrict__ pre,
+                                                                      const double* __restrict__ suf,
+                                                                      const double* __restrict__ bprior,
+                                                                      const double* __restrict__ bsuffix,
+                                                                      double* __restrict__ filt, float* __restrict__ ms,
+                                                                      float* __restrict__ Vs, int vs_diag) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G.K * G.nc) return;
+  constexpr int REC = D + D * D;
+  const int k = idx % G.K, j = idx / G.K;
+  Mat<double, D> F, sQ;
+  bool fid;
+  load_dynamics<double, D>(M, k, s[k], F, sQ, fid);
+  Vec<double, D> m, eta;
+  Mat<double, D> P, J;
+  dense_chunk_boundary<D>(G, M, k, j, j, pre, suf, bprior, bsuffix, m, P, eta, J);   // one element per lane (Bs == B)
+  const int t0 = j * G.B, len = min(G.B, G.T - t0);
+  const double ch = dense_robust_group_replay_chunk<D>(obs, lam, nu, last != 0, k, t0, len, F, sQ, fid, m, P, eta, J,
+                                                       filt + (size_t)t0 * REC * G.K + k, ms, Vs, vs_diag != 0,
+                                                       (size_t)G.K);
+  if (change && !last) robust_change_max(change + k, (float)ch);
+}
+
+size_t dense_smooth_robust_group_workspace_bytes(int T, int K, int D, int O, int g) {
+  return dense_generic_workspace_bytes(T, K, D, O, T, dense_robust_tail_bytes(T, K, O / g));
+}
+
+int dense_smooth_robust_group(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
+                              int g, int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs,
+                              void* ws, size_t ws_bytes, hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, O = d.obs_dim;
+  DensePass P;
+  const int rc = dense_pass_begin(d, Mm, T, dense_robust_tail_bytes(T, K, O / g), ws, ws_bytes, P);
+  if (rc != EKS_OK) return rc;
+  float* lam = weights ? weights : reinterpret_cast<float*>(P.tail);
+  const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
+  if (change) {
+    const hipError_t e = hipMemsetAsync(change, 0, (size_t)K * sizeof(float), st);
+    if (e != hipSuccess) return hip_status(e);
+  }
+  EKS_DISPATCH_D(d.state_dim, {
+    for (int it = 0; it < n_iters; ++it) {
+      const int last = it == n_iters - 1;
+      const RobustGroupObs<DD> obs =
+          make_robust_group_obs<DD>(y, var, (it > 0 || weights_in) ? lam : nullptr, K, O, g, P.M);
+      dense_prelude<DD>(P.G, P.M, P.s, obs, P.L, kGateOpen, "dense_robust_group_summarize", "dense_robust_group_scan",
+                        st);
+      dense_pass_launch(P, "dense_robust_group_replay", st, dense_robust_group_replay_kernel<DD>, obs, lam, nu, last,
                         it == n_iters - 2 ? change : nullptr, P.L.pre, P.L.suf, P.L.bprior, P.L.bsuffix, P.L.filt, ms,
                         Vs, vs_diag);
     }

@@ -168,6 +168,17 @@ size_t dense_smooth_robust_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double nu,
                         int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws,
                         size_t ws_bytes, hipStream_t st);
+// eks_smooth_robust with one weight per group of g consecutive coordinates, g dividing O (eks_smooth_robust_group.hip:
+// scalar chains, eks_smooth_robust's workspace plus a contribution plane and a combine launch; eks_dense.hip: general
+// models, always the generic kernels).  weights: [T][K][O / g]
+size_t diag_smooth_robust_group_workspace_bytes(int T, int N, int g);
+int diag_smooth_robust_group(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double nu, int g,
+                             int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws,
+                             size_t ws_bytes, hipStream_t st);
+size_t dense_smooth_robust_group_workspace_bytes(int T, int K, int D, int O, int g);
+int dense_smooth_robust_group(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double nu,
+                              int g, int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs,
+                              void* ws, size_t ws_bytes, hipStream_t st);
 // the smoother under Student-t process noise (eks_smooth_jumps.hip: scalar chains, eks_smooth_tv's shapes on
 // eks_em_stats' workspace plus a scale and a contribution plane, and the combine launch both paths share;
 // eks_dense.hip: general models, always the generic kernels)

@@ -284,6 +284,36 @@ def smooth_robust(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 8,
                             vs_diag, weights, weights_in, want_change)
 
 
+def smooth_robust_grouped(y, var, m0, S0, A, C, Q, s, group: int, nu: float = 4.0, n_iters: int = 8, flags: int = 0,
+                          vs_diag: bool = False, weights=None, weights_in: bool = False, want_change: bool = True):
+    """eks_smooth_robust_group: smooth_robust with one weight per `group` consecutive observed coordinates (`group`
+    divides O; 1 is smooth_robust itself).  `weights`: a float32 device tensor (T, K, O // group).  Returns
+    (ms, Vs, weights, change) as smooth_robust."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
+    dev = bufs[0].device
+    if int(group) != group or group < 1 or O % int(group):
+        raise ValueError(f'group must be a positive divisor of O = {O}, got {group}')
+    group = int(group)
+    if weights_in and weights is None:
+        raise ValueError('weights_in needs a weights tensor')
+    shape = (T, K, O // group)
+    if weights is None:
+        weights = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not weights.is_contiguous():
+        raise ValueError('weights must be contiguous: it is written in place')
+    weights = _chk(weights, torch.float32, 'weights', shape)
+    dims = _dims(K, T, D, O, _vs_flags(flags, vs_diag))
+    ms, Vs = _ms_Vs(T, K, D, vs_diag, dev)
+    change = torch.empty((K,), dtype=torch.float32, device=dev) if want_change else None
+    ws = _workspace(lib.eks_smooth_robust_group_workspace_bytes(ctypes.byref(dims), group), dev)
+    rc = lib.eks_smooth_robust_group(ctypes.byref(dims), *[_ptr(b) for b in bufs], float(nu), group, int(n_iters),
+                                     _ptr(weights), int(bool(weights_in)), _ptr(change), _ptr(ms), _ptr(Vs), _ptr(ws),
+                                     ws.numel(), _stream())
+    _lib.check(rc, 'eks_smooth_robust_group')
+    return ms, Vs, weights, change
+
+
 def smooth_jumps(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 12, flags: int = 0, vs_diag: bool = False,
                  scales=None, scales_in: bool = False, want_change: bool = True):
     """eks_smooth_jumps: eks_smooth under Student-t process noise with `nu` degrees of freedom, one scale per frame

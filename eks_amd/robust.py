@@ -15,10 +15,23 @@ residual of the frame.  The passes run on the device without a host round trip. 
     smooth_robust(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, nu=4.0, n_iters=8, ...) -> ms, Vs, weights, change
     smooth_singlecam_robust(marker_array, keypoint_names, s_finals, nu=4.0, n_iters=8, ...) -> dict(ms, Vs, weights)
 
+One weight per scalar observation treats the coordinates of a keypoint as unrelated evidence.  A paw swap moves x and y
+together and an occlusion spoils both coordinates of one view: the grouped forms give every `group` consecutive
+observed coordinates ONE weight (the multivariate Student-t of the same paper, lam_G = (nu + g) / (nu + sum of the
+group's delta)), so that a displacement which is ambiguous coordinate by coordinate counts jointly, and the caller gets
+one number per keypoint - or per view - and frame:
+
+    smooth_robust_grouped(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, group=2, ...) -> ms, Vs, weights, change
+    smooth_singlecam_robust_grouped(marker_array, keypoint_names, s_finals, ...) -> dict(ms, Vs, weights (T, K))
+    smooth_multicam_robust(marker_array, keypoint_names, camera_names, s_finals, avg_mode=, var_mode=, ...)
+        -> dict(ms, Vs, weights (T, K, V), reprojected)
+
 What it is not: nu is not fitted; s_finals comes from the drivers' search on the Gaussian model (there is no search
 under the robust model); the weights do not combine with a caller's process-noise scale, the sampler, increments, EM or
-innovations (with the Student-t scales of eks_amd.jumps they combine in eks_amd.heavy_tails); one weight per coordinate, not per keypoint.  A weight near (nu + 1) / nu says the frame agrees with its
-neighbours, a weight near 0 that it was discounted as an outlier.
+innovations (with the Student-t scales of eks_amd.jumps they combine in eks_amd.heavy_tails; the grouped weights do
+not); the multi-camera form has no variance inflation, no camgroup and no search; a grouped weight says that its group
+is wrong, not which coordinate of it.  A weight near (nu + g) / nu (g = 1 per coordinate) says the frame agrees with
+its neighbours, a weight near 0 that it was discounted as an outlier.
 """
 from __future__ import annotations
 
@@ -29,7 +42,8 @@ import numpy as np
 from . import hip_ops
 from ._problem import check_iteration_counts, iterated_smooth, singlecam_problem
 
-__all__ = ['smooth_robust', 'smooth_singlecam_robust']
+__all__ = ['smooth_robust', 'smooth_singlecam_robust', 'smooth_robust_grouped', 'smooth_singlecam_robust_grouped',
+           'smooth_multicam_robust']
 
 
 def smooth_robust(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, nu: float = 4.0, n_iters: int = 8, tol=None,
@@ -64,3 +78,91 @@ def smooth_singlecam_robust(marker_array, keypoint_names: list, s_finals, *, nu:
     return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)) + mu.astype(np.float32)[None],
                 Vs=np.ascontiguousarray(np.swapaxes(Vs, 0, 1)),
                 weights=np.ascontiguousarray(np.swapaxes(weights, 0, 1)))
+
+
+# ---- one weight per group of coordinates -------------------------------------------------------------------------------
+def smooth_robust_grouped(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, group: int, nu: float = 4.0,
+                          n_iters: int = 8, tol=None, max_iters: int = 64, vs_diag: bool = False,
+                          return_device: bool = False):
+    """smooth_robust with one weight per `group` consecutive observed coordinates (`group` divides O; 1 is
+    smooth_robust).  A coordinate whose variance is 1e30 or more is missing and leaves its group; a group with nothing
+    observed keeps weight 1.  Everything else as smooth_robust.
+
+    Returns (ms (K,T,D), Vs, weights (K,T,O // group) in (0, (nu + group) / nu], change (K,))."""
+    O = np.shape(ys)[-1] if np.ndim(ys) == 3 else 0
+    if isinstance(group, bool) or int(group) != group or group < 1 or (O and O % int(group)):
+        raise ValueError(f'group must be a positive divisor of the observation width {O}; got {group!r}')
+    group = int(group)
+
+    def op(*args, **kw):
+        return hip_ops.smooth_robust_grouped(*args, group=group, **kw)
+
+    return iterated_smooth('smooth_robust_grouped', op, 'weights', (ys, m0s, S0s, As, Cs, Qs, ensemble_vars), s_finals,
+                           nu, n_iters, tol, max_iters, vs_diag, return_device, None)
+
+
+def smooth_singlecam_robust_grouped(marker_array, keypoint_names: list, s_finals, *, nu: float = 4.0, n_iters: int = 8,
+                                    tol=None, max_iters: int = 64, avg_mode: Literal['mean', 'median'] = 'median',
+                                    var_mode: Literal['var', 'confidence_weighted_var'] = 'confidence_weighted_var'
+                                    ) -> dict:
+    """smooth_singlecam_robust with ONE weight per keypoint and frame (group = 2: x and y are wrong together).
+    Returns a dict of float32 arrays: ms, Vs (T, K, 2) as smooth_singlecam_robust, weights (T, K) in
+    (0, (nu + 2) / nu]."""
+    check_iteration_counts(nu, n_iters, tol, max_iters)
+    model, _, mu = singlecam_problem('smooth_singlecam_robust_grouped', marker_array, keypoint_names, avg_mode, var_mode)
+    ms, Vs, weights, _ = smooth_robust_grouped(*model, s_finals, group=2, nu=nu, n_iters=n_iters, tol=tol,
+                                               max_iters=max_iters, vs_diag=True)
+    return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)) + mu.astype(np.float32)[None],
+                Vs=np.ascontiguousarray(np.swapaxes(Vs, 0, 1)),
+                weights=np.ascontiguousarray(np.swapaxes(weights, 0, 1)[:, :, 0]))
+
+
+def multicam_problem(marker_array, keypoint_names, camera_names, quantile_keep_pca, avg_mode, var_mode, pca_object,
+                     n_latent):
+    """The linear multi-camera model as ensemble_kalman_smoother_multicam's host branch builds it: ensemble ->
+    centring -> per-keypoint PCA -> initialize_kalman_filter_pca; O = 2V with the coordinates of a view adjacent.
+    Returns (model, mu): model = (ys (K,T,2V), m0s, S0s, As, Cs, Qs, ensemble_vars (T,K,2V)), mu (K,2V) float64 the
+    centring means."""
+    from .core import ensemble
+    from .marker_array import mA_to_stacked_array
+    from .multicam_smoother import initialize_kalman_filter_pca
+    from .stats import compute_pca
+    from .utils import center_predictions
+    M, V, T, K, _ = marker_array.shape
+    if camera_names is None or len(camera_names) != V:
+        raise ValueError(f'{0 if camera_names is None else len(camera_names)} camera names for {V} views')
+    if len(keypoint_names) != K:
+        raise ValueError(f'{len(keypoint_names)} keypoint names for {K} keypoints')
+    if V < 2:
+        raise ValueError('smooth_multicam_robust takes a multi-view marker array')
+    ens = ensemble(marker_array, avg_mode=avg_mode, var_mode=var_mode)       # (1,V,T,K,5)
+    valid_mask, centered, good_centered, means = center_predictions(ens, quantile_keep_pca)
+    pcas, good_pcs = compute_pca(valid_mask, centered, good_centered, n_components=n_latent, pca_object=pca_object)
+    m0s, S0s, As, Qs, Cs = initialize_kalman_filter_pca(good_pcs, pcas, n_latent)
+    vars_ma = ens.slice_fields('var_x', 'var_y')
+    ys = np.stack([mA_to_stacked_array(centered, k) for k in range(K)])      # (K,T,2V)
+    evs = np.stack([mA_to_stacked_array(vars_ma, k) for k in range(K)])      # (K,T,2V)
+    mu = np.swapaxes(np.asarray(means.array)[0, :, 0], 0, 1).reshape(K, 2 * V)   # (V,K,2) -> (K,2V)
+    return (ys, m0s, S0s, As, Cs, Qs, np.ascontiguousarray(np.swapaxes(evs, 0, 1))), mu
+
+
+def smooth_multicam_robust(marker_array, keypoint_names: list, camera_names: list, s_finals, *, n_latent: int = 3,
+                           quantile_keep_pca: float = 50.0, avg_mode: Literal['mean', 'median'],
+                           var_mode: Literal['var', 'confidence_weighted_var'], pca_object=None, nu: float = 4.0,
+                           n_iters: int = 8, tol=None, max_iters: int = 64) -> dict:
+    """The linear multi-camera smoother under Student-t observation noise with ONE weight per view, keypoint and frame
+    (group = 2): an occluded or mislabelled view is discounted as a whole and the other views carry the frame.  The
+    model is rebuilt as ensemble_kalman_smoother_multicam's host branch builds it; there is no variance inflation, no
+    camgroup and no search - s_finals is what the Gaussian driver returned.  Returns a dict of float32 arrays in PIXEL
+    coordinates:
+        ms (T, K, n_latent), Vs (T, K, n_latent)   the latent state and its posterior variances
+        weights (T, K, V)                          one per view, in (0, (nu + 2) / nu]
+        reprojected (T, K, 2V)                     C ms with the centring means added back"""
+    check_iteration_counts(nu, n_iters, tol, max_iters)
+    model, mu = multicam_problem(marker_array, keypoint_names, camera_names, quantile_keep_pca, avg_mode, var_mode,
+                                 pca_object, n_latent)
+    ms, Vs, weights, _ = smooth_robust_grouped(*model, s_finals, group=2, nu=nu, n_iters=n_iters, tol=tol,
+                                               max_iters=max_iters, vs_diag=True)
+    rep = np.einsum('kod,ktd->tko', model[4], ms.astype(np.float64)) + mu[None]
+    return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)), Vs=np.ascontiguousarray(np.swapaxes(Vs, 0, 1)),
+                weights=np.ascontiguousarray(np.swapaxes(weights, 0, 1)), reprojected=rep.astype(np.float32))

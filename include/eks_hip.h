@@ -140,6 +140,30 @@ int eks_smooth_robust(const eks_dims_t* dims, const float* y, const float* var, 
                       float* weights, int32_t weights_in, float* change, float* ms, float* Vs, void* workspace,
                       size_t workspace_bytes, eks_stream_t stream);
 
+/* ---- eks_smooth_robust with ONE weight per group of `group` consecutive observed coordinates: the x and y of a
+ * single-camera keypoint, the two coordinates of one view of a multi-camera keypoint - what a paw swap or an occlusion
+ * spoils together.  The multivariate Student-t of Agamennoni, Nieto and Nebot: for group G of keypoint k at frame t
+ *     y_{t,G} | x_t, lam_{t,G} ~ N(C_G x_t, diag(r_{t,o}) / lam_{t,G}),    lam_{t,G} ~ Gamma(nu / 2, rate nu / 2).
+ * Passes, outputs, continuation and change are eks_smooth_robust's; a pass smooths under clip(r_{t,o} / lam_{t,G(o)}) and
+ * every pass but the last sets lam_{t,G} = (nu + g) / (nu + sum_{o in G} delta_{t,o}), in (0, (nu + g) / nu].  A
+ * coordinate whose clipped variance is 1e30 is missing: it is no evidence and leaves its group's Gamma factor (g counts
+ * the observed coordinates), so a group with nothing observed keeps weight 1.
+ *   group       >= 1 and a divisor of O (on scalar chains O = D), else EKS_ERR_SHAPE.  group = 1 IS eks_smooth_robust:
+ *               the call is forwarded and returns its bits.
+ *   weights     float32 [T][K][O / group]; NULL, weights_in as eks_smooth_robust.
+ *   scalar chains   the coordinates of a group are separate chains: a middle pass is six launches - summarize, the
+ *               three-launch scan, a replay that stores delta into a float32 [T][N] contribution plane, and a combine
+ *               launch, the only one that changes the weights; the last pass is five.  Workspace: eks_smooth_robust's
+ *               with the [T][N / group] plane, plus the contribution plane.
+ *   general models  eks_smooth_robust's kernels with the group sum in the lane; no combine launch.
+ * Every other refusal is eks_smooth_robust's, in its order, before anything is enqueued; the size query returns 0 for
+ * refused shapes. ------------------ */
+size_t eks_smooth_robust_group_workspace_bytes(const eks_dims_t* dims, int32_t group);
+int eks_smooth_robust_group(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,
+                            const double* A, const double* C, const double* Q, const double* s, double nu, int32_t group,
+                            int32_t n_iters, float* weights, int32_t weights_in, float* change, float* ms, float* Vs,
+                            void* workspace, size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- eks_smooth under Student-t PROCESS noise, for true fast movements (a paw reach, a saccade, a startle): a few
  * frames of motion far larger than the rest of the session, which one s per keypoint must either round off or follow
  * at the price of under-smoothing every still frame.  No reference counterpart.  One weight per keypoint and frame,
