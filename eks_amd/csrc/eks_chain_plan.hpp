@@ -4,6 +4,8 @@
 // (eks_em.hip), eks_innovations (eks_innov.hip) and eks_smooth_tv (eks_smooth_tv.hip).  The host part is plain C++:
 // tests/host_sim/ carves its buffers with the same chain_layout.  Kernels and launches: eks_chain.hip.
 #pragma once
+#include <utility>
+
 #include "eks_sample_lane.hpp"
 
 namespace eks {
@@ -89,6 +91,17 @@ inline ChainPlan chain_plan(int T, int N, int n_draws, bool with_part, void* ws)
   P.L = chain_map(N);
   P.blocks = chain_blocks(P.L, P.W.nc);
   return P;
+}
+
+// f(std::integral_constant<int, R>{}) for R == vs_row, PointerStore's VS_ROW as a compile-time constant: 0
+// (EKS_FLAG_VS_DIAG) or the state dimension 1 .. 8; any other value calls nothing
+template <typename F, int... R>
+inline void with_vs_row(int vs_row, F&& f, std::integer_sequence<int, R...>) {
+  (void)((vs_row == R && (f(std::integral_constant<int, R>{}), true)) || ...);
+}
+template <typename F>
+inline void with_vs_row(int vs_row, F&& f) {
+  with_vs_row(vs_row, f, std::make_integer_sequence<int, 9>{});
 }
 
 }  // namespace eks

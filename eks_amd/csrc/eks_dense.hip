@@ -636,32 +636,6 @@ size_t dense_smooth_robust_workspace_bytes(int T, int K, int D, int O) {
   return dense_generic_workspace_bytes(T, K, D, O, T, dense_robust_tail_bytes(T, K, O));
 }
 
-int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
-                        int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws,
-                        size_t ws_bytes, hipStream_t st) {
-  const int T = d.n_frames, K = d.n_keypoints, O = d.obs_dim;
-  DensePass P;
-  const int rc = dense_pass_begin(d, Mm, T, dense_robust_tail_bytes(T, K, O), ws, ws_bytes, P);
-  if (rc != EKS_OK) return rc;
-  float* lam = weights ? weights : reinterpret_cast<float*>(P.tail);
-  const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
-  if (change) {
-    const hipError_t e = hipMemsetAsync(change, 0, (size_t)K * sizeof(float), st);
-    if (e != hipSuccess) return hip_status(e);
-  }
-  EKS_DISPATCH_D(d.state_dim, {
-    for (int it = 0; it < n_iters; ++it) {
-      const int last = it == n_iters - 1;
-      const RobustObs<DD> obs = make_robust_obs<DD>(y, var, (it > 0 || weights_in) ? lam : nullptr, K, O, P.M);
-      dense_prelude<DD>(P.G, P.M, P.s, obs, P.L, kGateOpen, "dense_robust_summarize", "dense_robust_scan", st);
-      dense_pass_launch(P, "dense_robust_replay", st, dense_robust_replay_kernel<DD>, obs, lam, nu, last,
-                        it == n_iters - 2 ? change : nullptr, P.L.pre, P.L.suf, P.L.bprior, P.L.bsuffix, P.L.filt, ms,
-                        Vs, vs_diag);
-    }
-  })
-  return hip_status(hipGetLastError());
-}
-
 // ---- eks_smooth_robust_group: dense_smooth_robust with one weight per group of g coordinates -------------------------
 // The observation source reads lam[t][k][o / g] (eks_smooth_robust_group_lane.hpp: RobustGroupObs); the replay's emit
 // step holds every delta_o of its keypoint and frame, sums them per group and writes lam[t][k][G] in place: no combine
@@ -698,9 +672,14 @@ size_t dense_smooth_robust_group_workspace_bytes(int T, int K, int D, int O, int
   return dense_generic_workspace_bytes(T, K, D, O, T, dense_robust_tail_bytes(T, K, O / g));
 }
 
-int dense_smooth_robust_group(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
-                              int g, int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs,
-                              void* ws, size_t ws_bytes, hipStream_t st) {
+// One driver for both, on the observation source: RobustObs (g = 1) or RobustGroupObs.  They differ in how the source
+// is made, in the plane's width O / g and in the replay kernel.
+template <template <int> class Obs>
+static int dense_smooth_robust_on(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
+                                  int g, int n_iters, float* weights, int weights_in, float* change, float* ms,
+                                  float* Vs, void* ws, size_t ws_bytes, const char* summarize_scope,
+                                  const char* scan_scope, const char* replay_scope, hipStream_t st) {
+  constexpr bool kGrouped = std::is_same<Obs<1>, RobustGroupObs<1>>::value;
   const int T = d.n_frames, K = d.n_keypoints, O = d.obs_dim;
   DensePass P;
   const int rc = dense_pass_begin(d, Mm, T, dense_robust_tail_bytes(T, K, O / g), ws, ws_bytes, P);
@@ -714,21 +693,41 @@ int dense_smooth_robust_group(const eks_dims_t& d, const float* y, const float* 
   EKS_DISPATCH_D(d.state_dim, {
     for (int it = 0; it < n_iters; ++it) {
       const int last = it == n_iters - 1;
-      const RobustGroupObs<DD> obs =
-          make_robust_group_obs<DD>(y, var, (it > 0 || weights_in) ? lam : nullptr, K, O, g, P.M);
-      dense_prelude<DD>(P.G, P.M, P.s, obs, P.L, kGateOpen, "dense_robust_group_summarize", "dense_robust_group_scan",
-                        st);
-      dense_pass_launch(P, "dense_robust_group_replay", st, dense_robust_group_replay_kernel<DD>, obs, lam, nu, last,
-                        it == n_iters - 2 ? change : nullptr, P.L.pre, P.L.suf, P.L.bprior, P.L.bsuffix, P.L.filt, ms,
-                        Vs, vs_diag);
+      const float* lam_in = (it > 0 || weights_in) ? lam : nullptr;
+      Obs<DD> obs;
+      if constexpr (kGrouped) obs = make_robust_group_obs<DD>(y, var, lam_in, K, O, g, P.M);
+      else obs = make_robust_obs<DD>(y, var, lam_in, K, O, P.M);
+      dense_prelude<DD>(P.G, P.M, P.s, obs, P.L, kGateOpen, summarize_scope, scan_scope, st);
+      const auto replay = [&](auto kernel) {
+        dense_pass_launch(P, replay_scope, st, kernel, obs, lam, nu, last, it == n_iters - 2 ? change : nullptr, P.L.pre,
+                          P.L.suf, P.L.bprior, P.L.bsuffix, P.L.filt, ms, Vs, vs_diag);
+      };
+      if constexpr (kGrouped) replay(dense_robust_group_replay_kernel<DD>);
+      else replay(dense_robust_replay_kernel<DD>);
     }
   })
   return hip_status(hipGetLastError());
 }
 
+int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
+                        int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws,
+                        size_t ws_bytes, hipStream_t st) {
+  return dense_smooth_robust_on<RobustObs>(d, y, var, Mm, nu, 1, n_iters, weights, weights_in, change, ms, Vs, ws,
+                                           ws_bytes, "dense_robust_summarize", "dense_robust_scan",
+                                           "dense_robust_replay", st);
+}
+
+int dense_smooth_robust_group(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu,
+                              int g, int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs,
+                              void* ws, size_t ws_bytes, hipStream_t st) {
+  return dense_smooth_robust_on<RobustGroupObs>(d, y, var, Mm, nu, g, n_iters, weights, weights_in, change, ms, Vs, ws,
+                                                ws_bytes, "dense_robust_group_summarize", "dense_robust_group_scan",
+                                                "dense_robust_group_replay", st);
+}
+
 // ---- eks_smooth_jumps: n_iters passes of dense_smooth_tv's organisation under the scale plane -----------------------
 // A middle pass: the prelude under the plane, a replay (eks_smooth_jumps_lane.hpp) that writes delta_t into a [T][K]
-// float64 plane, and eks_smooth_jumps.hip's combine launch, the only one that changes the scales.  The last pass is
+// float64 plane, and eks_smooth_student.hip's combine launch, the only one that changes the scales.  The last pass is
 // dense_smooth_tv itself, on the front of the same workspace.  Tail: the [T][K] float scale plane (used when the caller
 // passes none), then the delta plane.
 template <int D>

@@ -158,7 +158,7 @@ int diag_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const 
 size_t dense_smooth_tv_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
                     const DenseModel& M, float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);
-// the smoother under Student-t observation noise (eks_smooth_robust.hip: scalar chains, eks_smooth_tv's shapes on
+// the smoother under Student-t observation noise (eks_smooth_student.hip: scalar chains, eks_smooth_tv's shapes on
 // eks_em_stats' workspace plus a plane of weights; eks_dense.hip: general models, always the generic kernels)
 size_t diag_smooth_robust_workspace_bytes(int T, int N);
 int diag_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double nu, int n_iters,
@@ -168,7 +168,7 @@ size_t dense_smooth_robust_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth_robust(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double nu,
                         int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs, void* ws,
                         size_t ws_bytes, hipStream_t st);
-// eks_smooth_robust with one weight per group of g consecutive coordinates, g dividing O (eks_smooth_robust_group.hip:
+// eks_smooth_robust with one weight per group of g consecutive coordinates, g dividing O (eks_smooth_student.hip:
 // scalar chains, eks_smooth_robust's workspace plus a contribution plane and a combine launch; eks_dense.hip: general
 // models, always the generic kernels).  weights: [T][K][O / g]
 size_t diag_smooth_robust_group_workspace_bytes(int T, int N, int g);
@@ -179,7 +179,7 @@ size_t dense_smooth_robust_group_workspace_bytes(int T, int K, int D, int O, int
 int dense_smooth_robust_group(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double nu,
                               int g, int n_iters, float* weights, int weights_in, float* change, float* ms, float* Vs,
                               void* ws, size_t ws_bytes, hipStream_t st);
-// the smoother under Student-t process noise (eks_smooth_jumps.hip: scalar chains, eks_smooth_tv's shapes on
+// the smoother under Student-t process noise (eks_smooth_student.hip: scalar chains, eks_smooth_tv's shapes on
 // eks_em_stats' workspace plus a scale and a contribution plane, and the combine launch both paths share;
 // eks_dense.hip: general models, always the generic kernels)
 size_t diag_smooth_jumps_workspace_bytes(int T, int K, int D);
@@ -193,7 +193,7 @@ int dense_smooth_jumps(const eks_dims_t& d, const float* y, const float* var, co
 int jumps_init_plane(float* plane, int T, int K, int scales_in, float* change, hipStream_t st);
 int jumps_combine(const void* contrib, bool f64, int nd, float* scales, float* change, int T, int K, double nu, int D,
                   hipStream_t st);
-// the smoother under Student-t noise on both sides (eks_smooth_heavy.hip: scalar chains, eks_smooth_tv's shapes on
+// the smoother under Student-t noise on both sides (eks_smooth_student.hip: scalar chains, eks_smooth_tv's shapes on
 // eks_em_stats' workspace plus a weight, a scale and a contribution plane; eks_dense.hip: general models, always the
 // generic kernels).  change: [2][K], row 0 the weights', row 1 the scales'
 size_t diag_smooth_heavy_workspace_bytes(int T, int K, int D);

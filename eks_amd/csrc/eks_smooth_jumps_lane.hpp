@@ -1,4 +1,4 @@
-// Lane-level bodies of eks_smooth_jumps (eks_smooth_jumps.hip: scalar chains and the combine kernel; eks_dense.hip:
+// Lane-level bodies of eks_smooth_jumps (eks_smooth_student.hip: scalar chains and the combine kernel; eks_dense.hip:
 // dense_smooth_jumps), shared unchanged with tests/host_sim/jumps_sim.cpp (plain loops).  No reference counterpart:
 // the reference's process noise is Gaussian with one s per keypoint (eks/core.py:274-295).
 //
@@ -50,50 +50,6 @@ EKS_HD void load_chunk_scale(const NoiseScale& ns, int t0, int len, float (&wv)[
   for (int i = 0; i < B; ++i) {
     if (FULL && i < B - 1) wv[i] = row[(unsigned)i * (unsigned)ns.stride];
     else if (FULL || i < len) wv[i] = i < left ? row[(unsigned)i * (unsigned)ns.stride] : 1.0f;
-  }
-}
-
-struct JumpsCall {
-  const float *y, *var;
-  const float* scales;   // [T][K]: w, read only
-  float* contrib;        // [T][N]: delta_{t,d}, rows 1 .. T-1 written
-  int T, K;
-};
-
-// Replay of chunk j of chain n in a middle pass: smooth_tv_replay_lane's forward pass, fuse, RTS backwards with no
-// output code; the step from frame t0 + i to t0 + i + 1 stores delta of frame t0 + i + 1, so the transition into the
-// following chunk belongs to THIS chunk and the phantom step past frame T-1 stores nothing.
-template <int B, bool UNIT>
-EKS_HD void jumps_replay_lane(const SampleWs& W, const DiagModel& M, const JumpsCall& c, int n, int j) {
-  const ChainParams<float> p = load_chain_params(M, n);
-  const NoiseScale ns{c.scales, c.K, n / M.D, c.T};
-  const int t0 = j * B, len = c.T - t0 < B ? c.T - t0 : B;
-  const size_t o = (size_t)j * W.N + n;
-  float v0[B], v1[B], wv[B], qv[B];
-  float m = W.pm[o], P = W.pP[o];
-  if (len == B) {
-    load_chunk<B, true>(c.y, c.var, W.N, n, t0, len, v0, v1);
-    load_chunk_scale<B, true>(ns, t0, len, wv);
-#pragma unroll
-    for (int i = 0; i < B; ++i) qv[i] = p.q_s * wv[i];
-    filter_loaded_tv<B, UNIT, true>(v0, v1, qv, len, p, m, P);
-  } else {
-    load_chunk<B>(c.y, c.var, W.N, n, t0, len, v0, v1);
-    load_chunk_scale<B>(ns, t0, len, wv);
-#pragma unroll
-    for (int i = 0; i < B; ++i)
-      if (i < len) qv[i] = p.q_s * wv[i];
-    filter_loaded_tv<B, UNIT>(v0, v1, qv, len, p, m, P);
-  }
-  fuse_info(m, P, W.sEta[o], W.sJ[o]);
-  float* out = c.contrib + (size_t)(t0 + 1) * (size_t)W.N + (unsigned)n;
-  const int left = c.T - (t0 + 1);
-#pragma unroll
-  for (int i = B - 1; i >= 0; --i) {
-    if (i < len) {
-      const float d = rts_step_jumps<float, UNIT>(m, P, v0[i], v1[i], with_q(p, p.q_s * wv[i]), wv[i]);
-      if (i < left) out[(size_t)i * (size_t)W.N] = d;
-    }
   }
 }
 

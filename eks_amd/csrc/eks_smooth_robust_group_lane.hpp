@@ -1,4 +1,4 @@
-// Lane-level bodies of eks_smooth_robust_group (eks_smooth_robust_group.hip: scalar chains and the combine kernel;
+// Lane-level bodies of eks_smooth_robust_group (eks_smooth_student.hip: scalar chains and the combine kernel;
 // eks_dense.hip: dense_smooth_robust_group), shared unchanged with tests/host_sim/robust_group_sim.cpp (plain loops).
 // No reference counterpart.
 //
@@ -22,89 +22,6 @@
 namespace eks {
 
 constexpr float kGroupMissing = -1.0f;   // a contribution that is no evidence (delta itself is never negative)
-
-struct RobustGroupCall {
-  const float *y, *var;
-  const float* lam;   // [T][NG]: the weights, read only (HAS_LAM)
-  float* contrib;     // [T][N]: delta_{t,d}, written by a middle pass
-  float *ms, *Vs;     // written by the last pass only
-  int T, g, NG;       // NG = N / g columns of the weight plane
-  const float* ones;  // [T] of 1.0f: eks_smooth_tv's qscale (eks_smooth_robust_lane.hpp says why)
-};
-
-// T1: eks_smooth_robust's summarize body with the weight read at [t][n / g].
-template <int B, bool UNIT, bool HAS_LAM>
-EKS_HD void robust_group_summarize_lane(const SampleWs& W, const DiagModel& M, const RobustGroupCall& c, int n, int j) {
-  const ChainParams<float> p = load_chain_params(M, n);
-  const int t0 = j * B, len = c.T - t0 < B ? c.T - t0 : B;
-  const NoiseScale ns{c.ones, 1, 0, c.T};
-  float yy[B], rr[B], lv[B], qv[B];
-  Elem<float> e;
-  if (len == B) {
-    load_chunk<B, true>(c.y, c.var, W.N, n, t0, len, yy, rr);
-    load_chunk_noise<B, true>(ns, t0, len, p.q_s, qv);
-    if constexpr (HAS_LAM) {
-      load_chunk_weights<B, true>(c.lam, c.NG, n / c.g, t0, len, lv);
-      reweight_chunk<B, true>(rr, lv, len);
-    }
-    e = summarize_loaded_tv<B, UNIT, true>(yy, rr, qv, len, p);
-  } else {
-    load_chunk<B>(c.y, c.var, W.N, n, t0, len, yy, rr);
-    load_chunk_noise<B>(ns, t0, len, p.q_s, qv);
-    if constexpr (HAS_LAM) {
-      load_chunk_weights<B>(c.lam, c.NG, n / c.g, t0, len, lv);
-      reweight_chunk<B>(rr, lv, len);
-    }
-    e = summarize_loaded_tv<B, UNIT>(yy, rr, qv, len, p);
-  }
-  const size_t o = (size_t)j * W.N + n;
-  W.eA[o] = e.A; W.eb[o] = e.b; W.eC[o] = e.C; W.eEta[o] = e.eta; W.eJ[o] = e.J;
-}
-
-// T3: replay of chunk j of chain n: filter in registers under r_eff, fuse, RTS backwards.
-//   LAST  : ms / Vs stream out through PointerStore; nothing else is written;
-//   !LAST : no output code; per frame delta from the belief just advanced to that frame, stored into the contribution
-//           plane (kGroupMissing where the frame's own variance sits at the ceiling).  y and clip_var(var) stay in
-//           registers for it (eks_smooth_robust's KEEP form).
-template <int B, bool UNIT, int VS_ROW, bool HAS_LAM, bool LAST>
-EKS_HD void robust_group_replay_lane(const SampleWs& W, const DiagModel& M, const RobustGroupCall& c, int n, int j) {
-  const ChainParams<float> p = load_chain_params(M, n);
-  const int t0 = j * B, len = c.T - t0 < B ? c.T - t0 : B;
-  const size_t o = (size_t)j * W.N + n;
-  const NoiseScale ns{c.ones, 1, 0, c.T};
-  float v0[B], v1[B], lv[B], y0[B], r0[B], qv[B];
-  float m = W.pm[o], P = W.pP[o];
-  auto forward = [&](auto full) {
-    constexpr bool FULL = decltype(full)::value;
-    load_chunk<B, FULL>(c.y, c.var, W.N, n, t0, len, v0, v1);
-    load_chunk_noise<B, FULL>(ns, t0, len, p.q_s, qv);
-    if constexpr (HAS_LAM) load_chunk_weights<B, FULL>(c.lam, c.NG, n / c.g, t0, len, lv);
-    if constexpr (!LAST) {
-#pragma unroll
-      for (int i = 0; i < B; ++i)
-        if (FULL || i < len) { y0[i] = v0[i]; r0[i] = clip_var(v1[i]); }
-    }
-    if constexpr (HAS_LAM) reweight_chunk<B, FULL>(v1, lv, len);
-    filter_loaded_tv<B, UNIT, FULL>(v0, v1, qv, len, p, m, P);
-  };
-  if (len == B) forward(std::true_type{});
-  else forward(std::false_type{});
-  fuse_info(m, P, W.sEta[o], W.sJ[o]);
-  if constexpr (LAST) {
-    smooth_rows_tv<B, UNIT>(v0, v1, qv, len, p, m, P, PointerStore<VS_ROW>{c.ms, c.Vs, W.N, n, n % M.D, t0});
-  } else {
-    float* out = c.contrib + (size_t)t0 * (size_t)W.N + (unsigned)n;
-#pragma unroll
-    for (int i = B - 1; i >= 0; --i) {
-      if (i < len) {
-        rts_step<float, UNIT>(m, P, v0[i], v1[i], with_q(p, qv[i]));
-        const float d = UNIT ? (y0[i] - m) : (y0[i] - p.c * m);
-        const float delta = (d * d + (UNIT ? P : p.c * p.c * P)) * rcp(r0[i]);
-        out[(size_t)i * (size_t)W.N] = r0[i] >= kVarCeil ? kGroupMissing : delta;
-      }
-    }
-  }
-}
 
 // the weight from a group's sum (float64: the lanes are few, and the weight is rounded ONCE, into the plane)
 EKS_HD float robust_group_weight(double nu, int g_obs, double sum) {

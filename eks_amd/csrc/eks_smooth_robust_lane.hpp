@@ -1,4 +1,4 @@
-// Lane-level bodies of eks_smooth_robust (eks_smooth_robust.hip: scalar chains; eks_dense.hip: dense_smooth_robust),
+// Lane-level bodies of eks_smooth_robust (eks_smooth_student.hip: scalar chains; eks_dense.hip: dense_smooth_robust),
 // shared unchanged with tests/host_sim/robust_sim.cpp (plain loops).  No reference counterpart: the reference's
 // observation noise is Gaussian with the ensemble variance (eks/core.py:182-186).
 //
@@ -44,23 +44,6 @@ EKS_HD void robust_change_max(float* dst, float v) {
 #endif
 }
 
-struct RobustCall {
-  const float *y, *var;
-  float* lam;       // [T][N]: the weights, read (HAS_LAM) and written in place
-  float* change;    // [K]: max |lam_new - lam_old| of this pass, or null
-  float *ms, *Vs;   // written by the last pass only
-  int T;
-  float nu, nu1, lam_max;   // nu, nu + 1 and (nu + 1) / nu, each rounded once from float64
-  const float* ones;        // [T] of 1.0f: eks_smooth_tv's qscale (see below)
-};
-
-// The frames run eks_smooth_tv's bodies (load_chunk_noise, summarize_loaded_tv, filter_loaded_tv, rts_step on with_q)
-// at the noise scale w = 1, read from a vector of ones like any other qscale.  The values are those of the constant-q
-// bodies (q_s * 1.0f is exact); what the loads buy is eks_smooth_tv's BITS on the device.  With q_s a plain operand
-// the compiler contracts `C rg + q_s` around C rg where eks_smooth_tv's `C rg + q_s w` is contracted around q_s w
-// (UNIT chains: ms 1 - 1024 ulp apart, measured), and a single w passed as an argument is shared by all frames, which
-// changes the multiply's use count and with it the same choice.  The loads hit one cache line per chunk.
-
 // the chunk's weights into registers (ordinary loads, B more in flight next to load_chunk's 2 B)
 template <int B, bool FULL = false>
 EKS_HD void load_chunk_weights(const float* __restrict__ lam, int N, int n, int t0, int len, float (&lv)[B]) {
@@ -75,95 +58,6 @@ EKS_HD void reweight_chunk(float (&rr)[B], const float (&lv)[B], int len) {
 #pragma unroll
   for (int i = 0; i < B; ++i)
     if (FULL || i < len) rr[i] = robust_var(rr[i], lv[i]);
-}
-
-// T1: element of chunk j of chain n under r_eff.  HAS_LAM == false (a call's first pass without input weights): lam
-// is 1 and the plane is not read - summarize_loaded_tv on (y, var) itself.
-template <int B, bool UNIT, bool HAS_LAM>
-EKS_HD void robust_summarize_lane(const SampleWs& W, const DiagModel& M, const RobustCall& c, int n, int j) {
-  const ChainParams<float> p = load_chain_params(M, n);
-  const int t0 = j * B, len = c.T - t0 < B ? c.T - t0 : B;
-  const NoiseScale ns{c.ones, 1, 0, c.T};
-  float yy[B], rr[B], lv[B], qv[B];
-  Elem<float> e;
-  if (len == B) {
-    load_chunk<B, true>(c.y, c.var, W.N, n, t0, len, yy, rr);
-    load_chunk_noise<B, true>(ns, t0, len, p.q_s, qv);
-    if constexpr (HAS_LAM) {
-      load_chunk_weights<B, true>(c.lam, W.N, n, t0, len, lv);
-      reweight_chunk<B, true>(rr, lv, len);
-    }
-    e = summarize_loaded_tv<B, UNIT, true>(yy, rr, qv, len, p);
-  } else {
-    load_chunk<B>(c.y, c.var, W.N, n, t0, len, yy, rr);
-    load_chunk_noise<B>(ns, t0, len, p.q_s, qv);
-    if constexpr (HAS_LAM) {
-      load_chunk_weights<B>(c.lam, W.N, n, t0, len, lv);
-      reweight_chunk<B>(rr, lv, len);
-    }
-    e = summarize_loaded_tv<B, UNIT>(yy, rr, qv, len, p);
-  }
-  const size_t o = (size_t)j * W.N + n;
-  W.eA[o] = e.A; W.eb[o] = e.b; W.eC[o] = e.C; W.eEta[o] = e.eta; W.eJ[o] = e.J;
-}
-
-// T3: replay of chunk j of chain n: filter in registers under r_eff, fuse, RTS backwards.
-//   LAST  : ms / Vs stream out through PointerStore, the weights stay (a pass that never read them writes the ones it
-//           smoothed under);
-//   !LAST : no output code at all; per frame delta from the smoothed (m, P), lam_new stored in place, and the lane's
-//           largest |lam_new - lam_old| goes to change[keypoint] when the call asks for it (the last update only).
-// The backward pass needs y_t and r_t again after (v0, v1) have become (mf, Pf).  KEEP: they stay in registers (2 B
-// more VGPRs); else they are loaded again there, frame by frame (the rows were read by this lane moments ago).
-// Full chunks load and filter without per-frame predicates; the backward pass is the predicated one.
-template <int B, bool UNIT, int VS_ROW, bool HAS_LAM, bool LAST, bool KEEP = true>
-EKS_HD void robust_replay_lane(const SampleWs& W, const DiagModel& M, const RobustCall& c, int n, int j) {
-  const ChainParams<float> p = load_chain_params(M, n);
-  const int t0 = j * B, len = c.T - t0 < B ? c.T - t0 : B;
-  const size_t o = (size_t)j * W.N + n;
-  const NoiseScale ns{c.ones, 1, 0, c.T};
-  float v0[B], v1[B], lv[B], y0[B], r0[B], qv[B];
-  float m = W.pm[o], P = W.pP[o];
-  auto forward = [&](auto full) {
-    constexpr bool FULL = decltype(full)::value;
-    load_chunk<B, FULL>(c.y, c.var, W.N, n, t0, len, v0, v1);
-    load_chunk_noise<B, FULL>(ns, t0, len, p.q_s, qv);
-    if constexpr (HAS_LAM) load_chunk_weights<B, FULL>(c.lam, W.N, n, t0, len, lv);
-    if constexpr (!LAST && KEEP) {
-#pragma unroll
-      for (int i = 0; i < B; ++i)
-        if (FULL || i < len) { y0[i] = v0[i]; r0[i] = clip_var(v1[i]); }
-    }
-    if constexpr (HAS_LAM) reweight_chunk<B, FULL>(v1, lv, len);
-    filter_loaded_tv<B, UNIT, FULL>(v0, v1, qv, len, p, m, P);
-  };
-  if (len == B) forward(std::true_type{});
-  else forward(std::false_type{});
-  fuse_info(m, P, W.sEta[o], W.sJ[o]);
-  if constexpr (LAST) {
-    smooth_rows_tv<B, UNIT>(v0, v1, qv, len, p, m, P, PointerStore<VS_ROW>{c.ms, c.Vs, W.N, n, n % M.D, t0});
-    if constexpr (!HAS_LAM) {
-#pragma unroll
-      for (int i = 0; i < B; ++i)
-        if (i < len) (c.lam + (size_t)(t0 + i) * (size_t)W.N)[(unsigned)n] = 1.0f;
-    }
-  } else {
-    const PointerRows rows{c.y, c.var, W.N, n, t0};
-    float ch = 0.0f;
-#pragma unroll
-    for (int i = B - 1; i >= 0; --i) {
-      if (i < len) {
-        rts_step<float, UNIT>(m, P, v0[i], v1[i], with_q(p, qv[i]));
-        const float y = KEEP ? y0[i] : rows.load_y(i);
-        const float r = KEEP ? r0[i] : clip_var(rows.load_var(i));
-        const float d = UNIT ? (y - m) : (y - p.c * m);
-        const float delta = (d * d + (UNIT ? P : p.c * p.c * P)) * rcp(r);
-        const float lam_new = robust_weight(c.nu, c.nu1, c.lam_max, delta);
-        ch = fmaxf(ch, fabsf(lam_new - (HAS_LAM ? lv[i] : 1.0f)));
-        (c.lam + (size_t)(t0 + i) * (size_t)W.N)[(unsigned)n] = lam_new;
-      }
-    }
-    if (c.change) robust_change_max(c.change + n / M.D, ch);
-  }
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -31,27 +31,6 @@ __global__ __launch_bounds__(256) void smooth_tv_replay_kernel(ChainMap L, Sampl
   smooth_tv_replay_lane<B, UNIT, VS_ROW>(W, M, c, n, j);
 }
 
-template <bool UNIT>
-static void launch_tv_replay(int vs_row, const ChainPlan& E, const DiagModel& M, const SmoothTvCall& c, hipStream_t st) {
-#define EKS_TV_REPLAY(R)                                                                                          \
-  case R:                                                                                                         \
-    hipLaunchKernelGGL((smooth_tv_replay_kernel<kChainChunk, UNIT, R>), dim3(E.blocks), dim3(256), 0, st, E.L, E.W, M, \
-                       c);                                                                                        \
-    break;
-  switch (vs_row) {
-    EKS_TV_REPLAY(0)
-    EKS_TV_REPLAY(1)
-    EKS_TV_REPLAY(2)
-    EKS_TV_REPLAY(3)
-    EKS_TV_REPLAY(4)
-    EKS_TV_REPLAY(5)
-    EKS_TV_REPLAY(6)
-    EKS_TV_REPLAY(7)
-    EKS_TV_REPLAY(8)
-  }
-#undef EKS_TV_REPLAY
-}
-
 // shapes the scalar-chain form takes (EKS_OK) or the status it refuses them with; nothing here touches the device
 int diag_smooth_tv_check(const eks_dims_t& d) {
   if (!(d.flags & EKS_FLAG_VS_DIAG) && d.state_dim > 8) return EKS_ERR_UNSUPPORTED;   // as diag_smooth
@@ -78,8 +57,11 @@ int diag_smooth_tv(const eks_dims_t& d, const float* y, const float* var, const 
   {
     ProfScope ps("smooth_tv_replay", st);
     const int vs_row = (d.flags & EKS_FLAG_VS_DIAG) ? 0 : D;
-    if (unit) launch_tv_replay<true>(vs_row, E, M, c, st);
-    else launch_tv_replay<false>(vs_row, E, M, c, st);
+    with_vs_row(vs_row, [&](auto r) {
+      constexpr int R = decltype(r)::value;
+      if (unit) hipLaunchKernelGGL((smooth_tv_replay_kernel<kChainChunk, true, R>), grid, block, 0, st, E.L, E.W, M, c);
+      else hipLaunchKernelGGL((smooth_tv_replay_kernel<kChainChunk, false, R>), grid, block, 0, st, E.L, E.W, M, c);
+    });
   }
   return hip_status(hipGetLastError());
 }

@@ -1,5 +1,5 @@
 // Host-side simulator of eks_smooth_heavy's arithmetic on scalar chains.  TEST INFRASTRUCTURE ONLY: a stand-alone
-// program that calls the lane bodies the gfx950 kernels call (eks_amd/csrc/eks_smooth_heavy_lane.hpp) from plain loops,
+// program that calls the lane bodies the gfx950 kernels call (eks_amd/csrc/eks_smooth_student_lane.hpp) from plain loops,
 // in the kernels' order of launches, on a workspace carved by chain_layout from a heap buffer of exactly the reported
 // size, a weight plane of exactly [T][N], a scale plane of exactly [T][K] and a contribution plane of exactly [T][N]
 // floats.  It is not a fallback and is never loaded into Python: tests/test_heavy_cpu.py builds it (plain, and with
@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "chain_sim.hpp"
-#include "eks_smooth_heavy_lane.hpp"
+#include "eks_smooth_student_lane.hpp"
 
 using namespace eks;
 
@@ -33,14 +33,14 @@ struct Result {
 };
 
 template <int B, bool UNIT, bool HAS_LAM>
-static void pass(const SampleWs& W, const DiagModel& M, const HeavyCall& c, int N, bool last) {
+static void pass(const SampleWs& W, const DiagModel& M, const StudentCall& c, int N, bool last) {
   for (int j = 0; j < W.nc; ++j)
-    for (int n = 0; n < N; ++n) heavy_summarize_lane<B, UNIT, HAS_LAM>(W, M, c, n, j);
+    for (int n = 0; n < N; ++n) student_summarize_lane<B, UNIT, HAS_LAM, kObsInPlace, true>(W, M, c, n, j);
   chain_sim_scan(W, M);
   for (int j = 0; j < W.nc; ++j)
     for (int n = 0; n < N; ++n) {
-      if (last) heavy_last_lane<B, UNIT, 0, HAS_LAM>(W, M, c, n, j);
-      else heavy_replay_lane<B, UNIT, HAS_LAM>(W, M, c, n, j);
+      if (last) student_last_lane<B, UNIT, 0, HAS_LAM, kObsInPlace, true>(W, M, c, n, j);
+      else student_replay_lane<B, UNIT, HAS_LAM, kObsInPlace, true>(W, M, c, n, j);
     }
 }
 
@@ -60,8 +60,8 @@ static Result run(const Problem& p) {
   for (int it = 0; it < p.n_iters; ++it) {
     const bool last = it == p.n_iters - 1, has_lam = it > 0 || (p.planes_in & 1);
     float* ch = it == p.n_iters - 2 ? r.change.data() : nullptr;
-    const HeavyCall c{p.y.data(), p.var.data(), r.lam.data(), r.w.data(), contrib.data(), ch, r.ms.data(), r.Vs.data(),
-                      p.T, K, (float)p.nu_obs, (float)(p.nu_obs + 1.0), (float)((p.nu_obs + 1.0) / p.nu_obs)};
+    const StudentCall c{p.y.data(), p.var.data(), r.lam.data(), r.w.data(), contrib.data(), ch, r.ms.data(), r.Vs.data(),
+                        p.T, K, (float)p.nu_obs, (float)(p.nu_obs + 1.0), (float)((p.nu_obs + 1.0) / p.nu_obs), p.N, 1};
     if (!last) std::fill(contrib.begin(), contrib.end(), NAN);
     if (has_lam) pass<B, UNIT, true>(S.W, M, c, p.N, last);
     else pass<B, UNIT, false>(S.W, M, c, p.N, last);

@@ -1,5 +1,5 @@
 // Host-side simulator of eks_smooth_jumps' arithmetic on scalar chains.  TEST INFRASTRUCTURE ONLY: a stand-alone
-// program that calls the lane bodies the gfx950 kernels call (eks_amd/csrc/eks_smooth_jumps_lane.hpp) from plain loops,
+// program that calls the lane bodies the gfx950 kernels call (eks_amd/csrc/eks_smooth_student_lane.hpp) from plain loops,
 // in the kernels' order of launches, on a workspace carved by chain_layout from a heap buffer of exactly the reported
 // size, a scale plane of exactly [T][K] and a contribution plane of exactly [T][N] floats.  It is not a fallback and is
 // never loaded into Python: tests/test_jumps_cpu.py builds it (plain, and with -fsanitize=address,undefined) and runs it.
@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "chain_sim.hpp"
-#include "eks_smooth_jumps_lane.hpp"
+#include "eks_smooth_student_lane.hpp"
 
 using namespace eks;
 
@@ -44,14 +44,15 @@ static Result run(const Problem& p) {
   r.change.assign(K, 0.0f);
   std::vector<float> contrib(TN);                           // exactly [T][N]
   const SmoothTvCall tv{p.y.data(), p.var.data(), r.w.data(), r.ms.data(), r.Vs.data(), p.T, K, 1};
-  const JumpsCall c{p.y.data(), p.var.data(), r.w.data(), contrib.data(), p.T, K};
+  const StudentCall c{p.y.data(), p.var.data(), nullptr, r.w.data(), contrib.data(), nullptr, nullptr, nullptr, p.T, K,
+                      0.0f, 0.0f, 0.0f, p.N, 1};
   for (int it = 0; it + 1 < p.n_iters; ++it) {
     for (int j = 0; j < S.W.nc; ++j)
       for (int n = 0; n < p.N; ++n) smooth_tv_summarize_lane<B, UNIT>(S.W, M, tv, n, j);
     chain_sim_scan(S.W, M);
     std::fill(contrib.begin(), contrib.end(), NAN);
     for (int j = 0; j < S.W.nc; ++j)
-      for (int n = 0; n < p.N; ++n) jumps_replay_lane<B, UNIT>(S.W, M, c, n, j);
+      for (int n = 0; n < p.N; ++n) student_replay_lane<B, UNIT, false, kObsFixed, true>(S.W, M, c, n, j);
     for (size_t i = p.N; i < TN; ++i) r.unwritten += contrib[i] != contrib[i];
     for (int t = 1; t < p.T; ++t)
       for (int k = 0; k < K; ++k) {

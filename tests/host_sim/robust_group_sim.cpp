@@ -1,5 +1,5 @@
 // Host-side simulator of eks_smooth_robust_group's arithmetic on scalar chains.  TEST INFRASTRUCTURE ONLY: a stand-alone
-// program that calls the lane bodies the gfx950 kernels call (eks_amd/csrc/eks_smooth_robust_group_lane.hpp) from plain
+// program that calls the lane bodies the gfx950 kernels call (eks_amd/csrc/eks_smooth_student_lane.hpp) from plain
 // loops, in the kernels' order of launches - summarize, scan, replay, combine - on a workspace carved by chain_layout
 // from a heap buffer of exactly the reported size and planes of exactly [T][N / g], [T][N] and [T].  It is not a
 // fallback and is never loaded into Python: tests/test_robust_group_cpu.py builds it (plain, and with
@@ -18,8 +18,7 @@
 #include <vector>
 
 #include "chain_sim.hpp"
-#include "eks_smooth_robust_group_lane.hpp"
-#include "eks_smooth_tv_lane.hpp"
+#include "eks_smooth_student_lane.hpp"
 
 using namespace eks;
 
@@ -36,14 +35,14 @@ struct Result {
 };
 
 template <int B, bool UNIT, bool HAS_LAM>
-static void pass(const SampleWs& W, const DiagModel& M, const RobustGroupCall& c, bool last) {
+static void pass(const SampleWs& W, const DiagModel& M, const StudentCall& c, bool last) {
   for (int j = 0; j < W.nc; ++j)
-    for (int n = 0; n < W.N; ++n) robust_group_summarize_lane<B, UNIT, HAS_LAM>(W, M, c, n, j);
+    for (int n = 0; n < W.N; ++n) student_summarize_lane<B, UNIT, HAS_LAM, kObsGrouped, false>(W, M, c, n, j);
   chain_sim_scan(W, M);
   for (int j = 0; j < W.nc; ++j)
     for (int n = 0; n < W.N; ++n) {
-      if (last) robust_group_replay_lane<B, UNIT, 0, HAS_LAM, true>(W, M, c, n, j);
-      else robust_group_replay_lane<B, UNIT, 0, HAS_LAM, false>(W, M, c, n, j);
+      if (last) student_last_lane<B, UNIT, 0, HAS_LAM, kObsGrouped, false>(W, M, c, n, j);
+      else student_replay_lane<B, UNIT, HAS_LAM, kObsGrouped, false>(W, M, c, n, j);
     }
 }
 
@@ -60,8 +59,8 @@ static Result run(const Problem& p) {
   std::vector<float> contrib(TN);                               // exactly [T][N]
   const std::vector<float> ones(p.T, 1.0f);                     // exactly [T]
   if (p.n_iters == 1 && !p.weights_in) r.lam.assign(TG, 1.0f);  // the driver's fill
-  const RobustGroupCall c{p.y.data(), p.var.data(), r.lam.data(), contrib.data(), r.ms.data(), r.Vs.data(),
-                          p.T, p.g, NG, ones.data()};
+  const StudentCall c{p.y.data(), p.var.data(), r.lam.data(), ones.data(), contrib.data(), nullptr, r.ms.data(),
+                      r.Vs.data(), p.T, K, 0.0f, 0.0f, 0.0f, NG, p.g};
   for (int it = 0; it < p.n_iters; ++it) {
     const bool last = it == p.n_iters - 1, has_lam = it > 0 || p.weights_in;
     if (!last) contrib.assign(TN, NAN);                         // poison: the replay owes every entry

@@ -1,5 +1,5 @@
 // Host-side simulator of eks_smooth_robust's arithmetic on scalar chains.  TEST INFRASTRUCTURE ONLY: a stand-alone
-// program that calls the lane bodies the gfx950 kernels call (eks_amd/csrc/eks_smooth_robust_lane.hpp) from plain loops,
+// program that calls the lane bodies the gfx950 kernels call (eks_amd/csrc/eks_smooth_student_lane.hpp) from plain loops,
 // in the kernels' order of passes, on a workspace carved by chain_layout from a heap buffer of exactly the reported
 // size.  It is not a fallback and is never loaded into Python: tests/test_robust_cpu.py builds it (plain, and with
 // -fsanitize=address,undefined) and runs it.
@@ -15,8 +15,7 @@
 #include <vector>
 
 #include "chain_sim.hpp"
-#include "eks_smooth_robust_lane.hpp"
-#include "eks_smooth_tv_lane.hpp"
+#include "eks_smooth_student_lane.hpp"
 
 using namespace eks;
 
@@ -33,15 +32,15 @@ struct Result {
 };
 
 template <int B, bool UNIT, bool HAS_LAM>
-static void pass(const SampleWs& W, const DiagModel& M, const RobustCall& c, bool last, Result* keep) {
+static void pass(const SampleWs& W, const DiagModel& M, const StudentCall& c, bool last, Result* keep) {
   for (int j = 0; j < W.nc; ++j)
-    for (int n = 0; n < W.N; ++n) robust_summarize_lane<B, UNIT, HAS_LAM>(W, M, c, n, j);
+    for (int n = 0; n < W.N; ++n) student_summarize_lane<B, UNIT, HAS_LAM, kObsInPlace, false>(W, M, c, n, j);
   chain_sim_scan(W, M);
   if (keep) keep->planes.assign(reinterpret_cast<const char*>(W.eA), reinterpret_cast<const char*>(W.eA) + keep->planes.size());
   for (int j = 0; j < W.nc; ++j)
     for (int n = 0; n < W.N; ++n) {
-      if (last) robust_replay_lane<B, UNIT, 0, HAS_LAM, true>(W, M, c, n, j);
-      else robust_replay_lane<B, UNIT, 0, HAS_LAM, false>(W, M, c, n, j);
+      if (last) student_last_lane<B, UNIT, 0, HAS_LAM, kObsInPlace, false>(W, M, c, n, j);
+      else student_replay_lane<B, UNIT, HAS_LAM, kObsInPlace, false>(W, M, c, n, j);
     }
 }
 
@@ -59,8 +58,9 @@ static Result run(const Problem& p) {
   const std::vector<float> ones(p.T, 1.0f);   // exactly [T]
   for (int it = 0; it < p.n_iters; ++it) {
     const bool last = it == p.n_iters - 1;
-    const RobustCall c{p.y.data(), p.var.data(), r.lam.data(), it == p.n_iters - 2 ? r.change.data() : nullptr,
-                       r.ms.data(), r.Vs.data(), p.T, (float)p.nu, (float)(p.nu + 1.0), (float)((p.nu + 1.0) / p.nu), ones.data()};
+    const StudentCall c{p.y.data(), p.var.data(), r.lam.data(), ones.data(), nullptr,
+                        it == p.n_iters - 2 ? r.change.data() : nullptr, r.ms.data(), r.Vs.data(), p.T, K, (float)p.nu,
+                        (float)(p.nu + 1.0), (float)((p.nu + 1.0) / p.nu), p.N, 1};
     if (it > 0 || p.weights_in) pass<B, UNIT, true>(S.W, M, c, last, it == 0 ? &r : nullptr);
     else pass<B, UNIT, false>(S.W, M, c, last, &r);
   }

@@ -1,4 +1,4 @@
-"""GPU: eks_smooth_heavy (eks_amd/csrc/eks_smooth_heavy.hip on scalar chains, dense_smooth_heavy in eks_dense.hip on
+"""GPU: eks_smooth_heavy (eks_amd/csrc/eks_smooth_student.hip on scalar chains, dense_smooth_heavy in eks_dense.hip on
 general models) and eks_amd.heavy_tails against the references of tests/heavy_ref.py, through the C ABI.
 
 Bars.  Scalar chains (float32 lanes), the project's rule (heavy_ref.bars): error / scale <= max(1e-5, 4 x the float32

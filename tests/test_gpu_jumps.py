@@ -1,4 +1,4 @@
-"""GPU: eks_smooth_jumps (eks_amd/csrc/eks_smooth_jumps.hip on scalar chains, dense_smooth_jumps in eks_dense.hip on
+"""GPU: eks_smooth_jumps (eks_amd/csrc/eks_smooth_student.hip on scalar chains, dense_smooth_jumps in eks_dense.hip on
 general models) and eks_amd.jumps against the references of tests/jumps_ref.py, through the C ABI.
 
 Bars.  Scalar chains (float32 lanes), the project's rule (jumps_ref.bars): error / scale <= max(1e-5, 4 x the float32

@@ -1,4 +1,4 @@
-"""GPU: eks_smooth_robust (eks_amd/csrc/eks_smooth_robust.hip on scalar chains, dense_smooth_robust in eks_dense.hip
+"""GPU: eks_smooth_robust (eks_amd/csrc/eks_smooth_student.hip on scalar chains, dense_smooth_robust in eks_dense.hip
 on general models) and eks_amd.robust against the references of tests/robust_ref.py, through the C ABI.
 
 Bars.  Scalar chains (float32 lanes), the project's rule (robust_ref.bars): error / scale <= max(1e-5, 4 x the float32

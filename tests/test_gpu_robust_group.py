@@ -1,4 +1,4 @@
-"""GPU: eks_smooth_robust_group (eks_amd/csrc/eks_smooth_robust_group.hip on scalar chains, dense_smooth_robust_group in
+"""GPU: eks_smooth_robust_group (eks_amd/csrc/eks_smooth_student.hip on scalar chains, dense_smooth_robust_group in
 eks_dense.hip on general models) and the grouped functions of eks_amd.robust against the references of
 tests/robust_group_ref.py, through the C ABI.
 

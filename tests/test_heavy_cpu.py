@@ -2,7 +2,7 @@
 evaluation from the joint posterior, its monotonicity over 32 passes, the two single-sided limits against
 tests/robust_ref.py and tests/jumps_ref.py, the dense references against the scalar one, what the model buys on the
 feature's session (six true jumps AND twelve displaced frames), the float32 lane arithmetic of
-eks_amd/csrc/eks_smooth_heavy_lane.hpp run from plain loops by the stand-alone tests/host_sim/heavy_sim.cpp (plain and
+eks_amd/csrc/eks_smooth_student_lane.hpp run from plain loops by the stand-alone tests/host_sim/heavy_sim.cpp (plain and
 under -fsanitize=address,undefined; never loaded into this process), the C ABI's refusals against eks_smooth_jumps' and
 the Python argument checks.
 

@@ -1,7 +1,7 @@
 """CPU: eks_smooth_jumps without a GPU - delta_t of tests/jumps_ref.py against the joint Gaussian posterior by plain
 linear algebra (random scales, singular Q), the variational bound's monotonicity over 32 passes, the Gaussian limit,
 what the method buys on the feature's session with six true jumps, the dense reference against the scalar one, the
-continuation pass counts, the float32 lane arithmetic of eks_amd/csrc/eks_smooth_jumps_lane.hpp run from plain loops by
+continuation pass counts, the float32 lane arithmetic of eks_amd/csrc/eks_smooth_student_lane.hpp run from plain loops by
 the stand-alone tests/host_sim/jumps_sim.cpp (plain and under -fsanitize=address,undefined; never loaded into this
 process), the C ABI's refusals and size queries, and the Python argument checks.
 

@@ -1,7 +1,7 @@
 """CPU: eks_smooth_robust without a GPU - the variational bound of tests/robust_ref.py against its term-by-term
 evaluation from the joint Gaussian posterior, its monotonicity over 32 passes, the Gaussian limit, what the method buys
 on sessions with displaced frames, the dense reference against the scalar one, the float32 lane arithmetic of
-eks_amd/csrc/eks_smooth_robust_lane.hpp run from plain loops by the stand-alone tests/host_sim/robust_sim.cpp (plain and
+eks_amd/csrc/eks_smooth_student_lane.hpp run from plain loops by the stand-alone tests/host_sim/robust_sim.cpp (plain and
 under -fsanitize=address,undefined; never loaded into this process), the C ABI's refusals and the Python argument
 checks.
 

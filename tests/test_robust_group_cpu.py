@@ -1,7 +1,7 @@
 """CPU: eks_smooth_robust_group without a GPU - the variational bound of tests/robust_group_ref.py against its
 term-by-term evaluation from the joint Gaussian posterior, its monotonicity over 32 passes, the reference's consistency
 (g = 1 is tests/robust_ref.py, the dense form on a diagonal model is the scalar one, large nu is the Gaussian smoother),
-the demonstration session, the float32 lane arithmetic of eks_amd/csrc/eks_smooth_robust_group_lane.hpp run from plain
+the demonstration session, the float32 lane arithmetic of eks_amd/csrc/eks_smooth_student_lane.hpp run from plain
 loops by the stand-alone tests/host_sim/robust_group_sim.cpp (plain and under -fsanitize=address,undefined; never loaded
 into this process), the C ABI's refusals and the Python argument checks.
 
