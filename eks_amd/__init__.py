@@ -31,6 +31,7 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'smooth_multicam_robust': 'robust',
         'smooth_jumps': 'jumps', 'smooth_singlecam_jumps': 'jumps',
         'smooth_heavy_tailed': 'heavy_tails', 'smooth_singlecam_heavy_tailed': 'heavy_tails',
+        'fit_heavy_tailed': 'heavy_tails', 'fit_singlecam_heavy_tailed': 'heavy_tails',
     }
     if name in table:
         return getattr(importlib.import_module(f'.{table[name]}', __name__), name)

@@ -47,6 +47,10 @@ SIGNATURES = {
     'eks_smooth_heavy_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
     'eks_smooth_heavy': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 8 + [c_double, c_double, c_int32, c_void_p, c_void_p,
                                                                            c_int32] + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    'eks_smooth_heavy_fit_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
+    'eks_smooth_heavy_fit': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 8
+                             + [c_double, c_double, c_int32, c_double, c_double, c_void_p, c_void_p, c_int32]
+                             + [c_void_p] * 5 + [c_size_t, c_void_p]),
     'eks_smooth_increments_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
     'eks_smooth_increments': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 14 + [c_size_t, c_void_p]),
     'eks_em_stats_workspace_bytes': (c_size_t, [POINTER(EksDims)]),

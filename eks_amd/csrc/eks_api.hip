@@ -20,7 +20,7 @@ static int check_dims(const eks_dims_t* d) {
   return EKS_OK;
 }
 
-// The model-taking entries (eks_smooth, _tv, _robust, _robust_group, _jumps, _heavy, _increments, eks_em_stats, eks_innovations, eks_sample,
+// The model-taking entries (eks_smooth, _tv, _robust, _robust_group, _jumps, _heavy, _heavy_fit, _increments, eks_em_stats, eks_innovations, eks_sample,
 // eks_nll, eks_nll_argmin) share one tail, stated once here.  Each entry keeps its own shape check in front of it; the
 // ORDER of an entry's checks is part of its contract (tests/test_api_refusals_cpu.py pins every status).
 
@@ -233,6 +233,56 @@ int eks_smooth_heavy(const eks_dims_t* d, const float* y, const float* var, cons
                                   : workspace_status(workspace, workspace_bytes, eks_smooth_heavy_workspace_bytes(d)),
       [&](const DiagModel& M) { return run(diag_smooth_heavy, M); },
       [&](const DenseModel& M) { return run(dense_smooth_heavy, M); });
+}
+
+// shapes eks_smooth_heavy_fit takes: eks_smooth_heavy's with T >= 2 (n = D (T - 1) divides)
+static int heavy_fit_check(const eks_dims_t* d) {
+  const int rc = smooth_tv_check(d);
+  if (rc != EKS_OK) return rc;
+  return d->n_frames < 2 ? EKS_ERR_SHAPE : EKS_OK;
+}
+
+size_t eks_smooth_heavy_fit_workspace_bytes(const eks_dims_t* d) {
+  return model_bytes(
+      d, heavy_fit_check(d),
+      [d](int T, int) { return diag_smooth_heavy_fit_workspace_bytes(T, d->n_keypoints, d->state_dim); },
+      dense_smooth_heavy_fit_workspace_bytes);
+}
+
+// eks_smooth_heavy's order with the fit's own refusals behind the shapes: shapes and T >= 2; either nu (+inf allowed),
+// the bounds, n_iters and an input plane on a Gaussian side (EKS_ERR_SHAPE); nu_obs = +inf on a general model
+// (EKS_ERR_UNSUPPORTED); the model's pointers; s_out, the outputs and a plane that is to be read; the workspace, its
+// size.  Only then is anything enqueued: the copy of s into s_out first.
+int eks_smooth_heavy_fit(const eks_dims_t* d, const float* y, const float* var, const double* m0, const double* S0,
+                         const double* A, const double* C, const double* Q, const double* s, double nu_obs,
+                         double nu_proc, int32_t n_iters, double log_s_lo, double log_s_hi, float* weights,
+                         float* scales, int32_t planes_in, float* change, double* s_out, float* ms, float* Vs,
+                         void* workspace, size_t workspace_bytes, eks_stream_t stream) {
+  const int rc = heavy_fit_check(d);
+  if (rc != EKS_OK) return rc;
+  const bool obs_gauss = nu_obs > 1.7e308, proc_gauss = nu_proc > 1.7e308;
+  if (!(nu_obs > 0.0) || !(nu_proc > 0.0) || n_iters < 1) return EKS_ERR_SHAPE;
+  if (!(log_s_lo <= log_s_hi) || !(log_s_lo >= -1.7e308) || !(log_s_hi <= 1.7e308)) return EKS_ERR_SHAPE;
+  if ((obs_gauss && (planes_in & 1)) || (proc_gauss && (planes_in & 2))) return EKS_ERR_SHAPE;
+  if (obs_gauss && !(d->flags & EKS_FLAG_DIAG_MODEL)) return EKS_ERR_UNSUPPORTED;
+  const bool plane_missing = ((planes_in & 1) && !weights) || ((planes_in & 2) && !scales);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  auto run = [&](auto kernels, auto M) {
+    if (s_out != s) {
+      const hipError_t e = hipMemcpyAsync(s_out, s, (size_t)d->n_keypoints * sizeof(double), hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) return EKS_ERR_HIP_BASE - (int)e;
+    }
+    M.s = s_out;
+    return kernels(*d, y, var, M, s_out, nu_obs, nu_proc, n_iters, log_s_lo, log_s_hi, weights, scales, planes_in, change,
+                   ms, Vs, workspace, workspace_bytes, st);
+  };
+  return model_call(
+      d, {y, var, m0, S0, A, C, Q, s},
+      !s_out || !ms || !Vs || plane_missing
+          ? EKS_ERR_NULL
+          : workspace_status(workspace, workspace_bytes, eks_smooth_heavy_fit_workspace_bytes(d)),
+      [&](const DiagModel& M) { return run(diag_smooth_heavy_fit, M); },
+      [&](const DenseModel& M) { return run(dense_smooth_heavy_fit, M); });
 }
 
 // shapes eks_smooth_increments takes (EKS_OK) or the status it refuses them with; nothing here touches the device

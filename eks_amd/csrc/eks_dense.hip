@@ -853,13 +853,17 @@ size_t dense_smooth_heavy_workspace_bytes(int T, int K, int D, int O) {
   return dense_generic_workspace_bytes(T, K, D, O, T, dense_heavy_tail_bytes(T, K, O));
 }
 
-int dense_smooth_heavy(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu_obs,
-                       double nu_proc, int n_iters, float* weights, float* scales, int planes_in, float* change,
-                       float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st) {
+// fit: eks_smooth_heavy_fit's M-step for s behind every middle pass' updates (eks_smooth_heavy_fit.hip), or null; with
+// it the tail ends with the fit's region (partial sums, tile tickets), change is [3][K] and a Gaussian process side skips the combine
+static int dense_heavy_run(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu_obs,
+                           double nu_proc, int n_iters, float* weights, float* scales, int planes_in, float* change,
+                           float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st, const HeavyFit* fit) {
   const int T = d.n_frames, K = d.n_keypoints, O = d.obs_dim;
   DensePass P;
-  int rc = dense_pass_begin(d, Mm, T, dense_heavy_tail_bytes(T, K, O), ws, ws_bytes, P);
+  int rc = dense_pass_begin(d, Mm, T, dense_heavy_tail_bytes(T, K, O) + (fit ? heavy_fit_part_bytes(T, K) : 0), ws,
+                            ws_bytes, P);
   if (rc != EKS_OK) return rc;
+  char* fit_ws = P.tail + dense_heavy_tail_bytes(T, K, O);
   char* tail = P.tail;
   float* lam = weights ? weights : reinterpret_cast<float*>(tail);
   tail += dense_robust_tail_bytes(T, K, O);
@@ -868,9 +872,11 @@ int dense_smooth_heavy(const eks_dims_t& d, const float* y, const float* var, co
   rc = jumps_init_plane(plane, T, K, planes_in & 2, nullptr, st);
   if (rc != EKS_OK) return rc;
   if (change) {
-    const hipError_t e = hipMemsetAsync(change, 0, 2 * (size_t)K * sizeof(float), st);
+    const hipError_t e = hipMemsetAsync(change, 0, (fit ? 3 : 2) * (size_t)K * sizeof(float), st);
     if (e != hipSuccess) return hip_status(e);
   }
+  if (fit) rc = heavy_fit_begin(fit_ws, T, K, st);
+  if (rc != EKS_OK) return rc;
   const int vs_diag = (d.flags & EKS_FLAG_VS_DIAG) ? 1 : 0;
   EKS_DISPATCH_D(d.state_dim, {
     for (int it = 0; it < n_iters; ++it) {
@@ -885,13 +891,40 @@ int dense_smooth_heavy(const eks_dims_t& d, const float* y, const float* var, co
       }
       dense_pass_launch(P, "dense_heavy_replay", st, dense_heavy_replay_kernel<DD>, obs, plane, lam, nu_obs, last, ch,
                         P.L.pre, P.L.suf, P.L.bprior, P.L.bsuffix, P.L.filt, delta, ms, Vs, vs_diag);
-      if (!last) {
+      if (!last && !(fit && fit->proc_gauss)) {
         rc = jumps_combine(delta, true, 1, plane, ch ? ch + K : nullptr, T, K, nu_proc, DD, st);
+        if (rc != EKS_OK) return rc;
+      }
+      if (!last && fit) {
+        rc = heavy_fit_step(delta, true, 1, plane, T, K, DD, fit->lo, fit->hi, fit_ws, fit->s,
+                            change ? change + 2 * K : nullptr, st);
         if (rc != EKS_OK) return rc;
       }
     }
   })
   return hip_status(hipGetLastError());
+}
+
+int dense_smooth_heavy(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double nu_obs,
+                       double nu_proc, int n_iters, float* weights, float* scales, int planes_in, float* change,
+                       float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st) {
+  return dense_heavy_run(d, y, var, Mm, nu_obs, nu_proc, n_iters, weights, scales, planes_in, change, ms, Vs, ws,
+                         ws_bytes, st, nullptr);
+}
+
+// eks_smooth_heavy_fit on general models: nu_obs finite (the entry refuses +inf), nu_proc finite or +inf; Mm.s == s_out
+size_t dense_smooth_heavy_fit_workspace_bytes(int T, int K, int D, int O) {
+  const size_t base = dense_smooth_heavy_workspace_bytes(T, K, D, O);
+  return base ? base + heavy_fit_part_bytes(T, K) : 0;
+}
+
+int dense_smooth_heavy_fit(const eks_dims_t& d, const float* y, const float* var, const DenseModel& Mm, double* s_out,
+                           double nu_obs, double nu_proc, int n_iters, double lo, double hi, float* weights,
+                           float* scales, int planes_in, float* change, float* ms, float* Vs, void* ws, size_t ws_bytes,
+                           hipStream_t st) {
+  const HeavyFit fit{s_out, lo, hi, !(nu_proc <= 1.7e308)};
+  return dense_heavy_run(d, y, var, Mm, nu_obs, nu_proc, n_iters, weights, scales, planes_in, change, ms, Vs, ws,
+                         ws_bytes, st, &fit);
 }
 
 // ---- eks_em_stats: dense_increments' organisation with the outputs replaced by a sum --------------------------------

@@ -204,6 +204,28 @@ size_t dense_smooth_heavy_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth_heavy(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double nu_obs,
                        double nu_proc, int n_iters, float* weights, float* scales, int planes_in, float* change,
                        float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);
+// eks_smooth_heavy with the M-step for s behind every middle pass' updates (eks_smooth_heavy_fit.hip: the fixed-order
+// reduction of S_k and the step, one launch; eks_smooth_student.hip and eks_dense.hip: the drivers' loops).  s_out is
+// the vector the model reads (M.s == s_out); a nu of +inf is a Gaussian side; change: [3][K]
+struct HeavyFit {
+  double* s;          // [K], read by every pass and stepped between passes
+  double lo, hi;      // bounds of log s
+  bool proc_gauss;    // nu_proc = +inf: no combine launch, the scale plane stays at ones
+};
+size_t heavy_fit_part_bytes(int T, int K);                             // the fit's region: partial sums and tile tickets
+int heavy_fit_begin(void* fit_ws, int T, int K, hipStream_t st);       // once a call: zeroes the tickets
+int heavy_fit_step(const void* contrib, bool f64, int nd, const float* scales, int T, int K, int D, double lo,
+                   double hi, void* fit_ws, double* s, float* dlog, hipStream_t st);
+size_t diag_smooth_heavy_fit_workspace_bytes(int T, int K, int D);
+int diag_smooth_heavy_fit(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double* s_out,
+                          double nu_obs, double nu_proc, int n_iters, double lo, double hi, float* weights,
+                          float* scales, int planes_in, float* change, float* ms, float* Vs, void* ws, size_t ws_bytes,
+                          hipStream_t st);
+size_t dense_smooth_heavy_fit_workspace_bytes(int T, int K, int D, int O);
+int dense_smooth_heavy_fit(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M, double* s_out,
+                           double nu_obs, double nu_proc, int n_iters, double lo, double hi, float* weights,
+                           float* scales, int planes_in, float* change, float* ms, float* Vs, void* ws, size_t ws_bytes,
+                           hipStream_t st);
 size_t dense_smooth_workspace_bytes(int T, int K, int D, int O);
 int dense_smooth(const eks_dims_t& d, const float* y, const float* var, const DenseModel& M,
                  float* ms, float* Vs, void* ws, size_t ws_bytes, hipStream_t st);

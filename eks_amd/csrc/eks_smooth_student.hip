@@ -25,6 +25,8 @@
 // eks_smooth_tv's bodies at w = 1, read from a [T] vector of ones in the workspace (eks_smooth_student_lane.hpp says
 // why).  The windowed replay of eks_smooth is never taken.  General models: eks_dense.hip, dense_smooth_robust,
 // dense_smooth_jumps, dense_smooth_heavy; jumps_combine also serves them, with one float64 contribution per keypoint.
+// eks_smooth_heavy_fit is the same driver with the M-step for s behind every middle pass' updates: one launch of
+// eks_smooth_heavy_fit.hip (heavy_fit) that reads the contribution and the scale plane once more.
 #include <hip/hip_runtime.h>
 
 #include "eks_chain_plan.hpp"
@@ -220,16 +222,19 @@ static StudentLayout student_layout(int T, int K, int D, int g) {
   return student_layout(T, N, OBS == kObsFixed ? 0 : N / g, PROC ? K : 1, OBS == kObsGrouped || PROC ? N : 0);
 }
 
+// fit: eks_smooth_heavy_fit's M-step for s behind every middle pass' updates (eks_smooth_heavy_fit.hip), or null.  With
+// it change is [3][K] - weights, scales, log s - whatever OBS is, and a Gaussian process side (nu_proc = +inf) skips
+// the combine launch: its plane of ones is already there.
 template <ObsSide OBS, bool PROC>
 static int student_smooth(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M,
                           const StudentSpec& s, int n_iters, float* ms, float* Vs, void* ws, size_t ws_bytes,
-                          hipStream_t st) {
+                          hipStream_t st, const HeavyFit* fit = nullptr) {
   static_assert(!(OBS == kObsGrouped && PROC), "one contribution plane: a pass stores either side's delta into it");
   const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, N = K * D, NG = N / s.g;
   int rc = diag_smooth_tv_check(d);
   if (rc != EKS_OK) return rc;
   const StudentLayout lay = student_layout<OBS, PROC>(T, K, D, s.g);
-  if (ws_bytes < lay.total) return EKS_ERR_WORKSPACE;
+  if (ws_bytes < lay.total + (fit ? heavy_fit_part_bytes(T, K) : 0)) return EKS_ERR_WORKSPACE;
   const ChainPlan E = chain_plan(T, N, 0, true, ws);
   char* base = static_cast<char*>(ws);
   float* lam = s.weights ? s.weights : reinterpret_cast<float*>(base + lay.lam);
@@ -245,8 +250,10 @@ static int student_smooth(const eks_dims_t& d, const float* y, const float* var,
     if (OBS == kObsGrouped && e == hipSuccess && n_iters == 1 && !s.weights_in)
       e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lam), 0x3f800000, (size_t)T * (size_t)NG, st);
     if (e == hipSuccess && s.change)
-      e = hipMemsetAsync(s.change, 0, (size_t)((OBS != kObsFixed) + PROC) * (size_t)K * sizeof(float), st);
+      e = hipMemsetAsync(s.change, 0, (size_t)(fit ? 3 : (OBS != kObsFixed) + PROC) * (size_t)K * sizeof(float), st);
     if (e != hipSuccess) return hip_status(e);
+    if (fit) rc = heavy_fit_begin(base + lay.total, T, K, st);
+    if (rc != EKS_OK) return rc;
   }
   const bool unit = (d.flags & EKS_FLAG_UNIT_AC) != 0;
   const int vs_row = (d.flags & EKS_FLAG_VS_DIAG) ? 0 : D;
@@ -256,7 +263,7 @@ static int student_smooth(const eks_dims_t& d, const float* y, const float* var,
     if (OBS == kObsFixed && last) return diag_smooth_tv(d, y, var, scales, 1, M, ms, Vs, ws, ws_bytes, st);
     // change: the last update of either plane is that of the pass before the last
     float* ch = it == n_iters - 2 ? s.change : nullptr;
-    float* ch_proc = ch && OBS != kObsFixed ? ch + K : ch;
+    float* ch_proc = ch && (OBS != kObsFixed || fit) ? ch + K : ch;
     const StudentCall c{y, var, lam, scales, contrib, ch, ms, Vs, T, K, (float)s.nu_obs, (float)(s.nu_obs + 1.0),
                         (float)((s.nu_obs + 1.0) / s.nu_obs), NG, s.g};
     rc = select_student_pass<OBS, PROC>(s, unit, has_lam, last, vs_row, E, M, c, st);
@@ -269,8 +276,15 @@ static int student_smooth(const eks_dims_t& d, const float* y, const float* var,
                          s.g, lam, ch, T, NG, D / s.g, K, s.nu_obs, has_lam ? 1 : 0);
     }
     if constexpr (PROC) {
-      rc = jumps_combine(contrib, false, D, scales, ch_proc, T, K, s.nu_proc, D, st);
-      if (rc != EKS_OK) return rc;
+      if (!(fit && fit->proc_gauss)) {
+        rc = jumps_combine(contrib, false, D, scales, ch_proc, T, K, s.nu_proc, D, st);
+        if (rc != EKS_OK) return rc;
+      }
+      if (fit) {
+        rc = heavy_fit_step(contrib, false, D, scales, T, K, D, fit->lo, fit->hi, base + lay.total, fit->s,
+                            s.change ? s.change + 2 * K : nullptr, st);
+        if (rc != EKS_OK) return rc;
+      }
     }
   }
   return hip_status(hipGetLastError());
@@ -317,6 +331,34 @@ int diag_smooth_heavy(const eks_dims_t& d, const float* y, const float* var, con
   const StudentSpec s{"heavy_summarize", "heavy_scan", "heavy_replay", nullptr, 1, nu_obs, nu_proc, weights,
                       planes_in & 1, scales, planes_in & 2, change};
   return student_smooth<kObsInPlace, true>(d, y, var, M, s, n_iters, ms, Vs, ws, ws_bytes, st);
+}
+
+// eks_smooth_heavy_fit on scalar chains: the driver above with the M-step for s.  A finite nu_obs runs the heavy
+// kernels, nu_obs = +inf eks_smooth_jumps' (no weight plane; the caller's, if any, comes back as ones).  The size is the
+// wider of the two layouts plus the fit's region ([slabs][K] partial sums, tile tickets), whatever the nu.
+size_t diag_smooth_heavy_fit_workspace_bytes(int T, int K, int D) {
+  return student_layout<kObsInPlace, true>(T, K, D, 1).total + heavy_fit_part_bytes(T, K);
+}
+
+int diag_smooth_heavy_fit(const eks_dims_t& d, const float* y, const float* var, const DiagModel& M, double* s_out,
+                          double nu_obs, double nu_proc, int n_iters, double lo, double hi, float* weights,
+                          float* scales, int planes_in, float* change, float* ms, float* Vs, void* ws, size_t ws_bytes,
+                          hipStream_t st) {
+  const HeavyFit fit{s_out, lo, hi, !(nu_proc <= 1.7e308)};
+  if (nu_obs <= 1.7e308) {
+    const StudentSpec s{"heavy_summarize", "heavy_scan", "heavy_replay", nullptr, 1, nu_obs, nu_proc, weights,
+                        planes_in & 1, scales, planes_in & 2, change};
+    return student_smooth<kObsInPlace, true>(d, y, var, M, s, n_iters, ms, Vs, ws, ws_bytes, st, &fit);
+  }
+  if (ws_bytes < diag_smooth_heavy_fit_workspace_bytes(d.n_frames, d.n_keypoints, d.state_dim)) return EKS_ERR_WORKSPACE;
+  if (weights) {
+    const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(weights), 0x3f800000,
+                                           (size_t)d.n_frames * (size_t)d.n_keypoints * (size_t)d.state_dim, st);   // 1.0f
+    if (e != hipSuccess) return hip_status(e);
+  }
+  const StudentSpec s{"jumps_summarize", "jumps_scan", "jumps_replay", nullptr, 1, 1.0, nu_proc, nullptr, 0, scales,
+                      planes_in & 2, change};
+  return student_smooth<kObsFixed, true>(d, y, var, M, s, n_iters, ms, Vs, ws, ws_bytes, st, &fit);
 }
 
 }  // namespace eks

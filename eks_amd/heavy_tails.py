@@ -17,6 +17,9 @@ counterpart.
     smooth_heavy_tailed(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, nu_obs=4.0, nu_proc=4.0, n_iters=12, ...)
         -> ms, Vs, weights, scales, change
     smooth_singlecam_heavy_tailed(marker_array, keypoint_names, s_finals, ...) -> dict(ms, Vs, weights, scales)
+    fit_heavy_tailed(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_init, nu_obs=4.0, nu_proc=4.0, n_iters=40, ...)
+        -> ms, Vs, weights, scales, s_fit, change
+    fit_singlecam_heavy_tailed(marker_array, keypoint_names, s_init, ...) -> dict(ms, Vs, weights, scales, s_fit)
 
 A weight near 1 says the observation agrees with the trajectory, a weight near 0 that it was discounted; a scale near 1
 says the frame moved like the rest of the session, a scale of hundreds or thousands marks a jump INTO that frame.
@@ -24,12 +27,22 @@ says the frame moved like the rest of the session, a scale of hundreds or thousa
 What the model cannot tell apart: a jump into frame 1 under a wide prior, a jump into the last frame, and two opposite
 jumps in consecutive frames each have an outlier explanation that costs less, and are treated as outliers.
 
-What it is not: neither nu is fitted; s_finals comes from the drivers' search on the Gaussian model; one side cannot
-be frozen; the planes do not combine with a caller's own frame-interval scale, the sampler, increments, EM or
-innovations.
+The smoothing parameter.  The drivers' search fits s to the Gaussian model, which explains displaced observations as
+process noise: on a session with outliers that s is far too large (over a thousand times on
+tests/heavy_fit_ref.py's outlier_session), and the smooth_* functions here take it as given.  The fit_* functions fit s inside the iteration: after every middle
+pass' updates of the planes, s <- s sum_t u_t delta_t / (D (T - 1)), the M-step of the same bound, on the device with no
+host round trip.  It is EM and nothing more: start it from a SMALL s.  Under a finite nu_proc, from a start 10 .. 100
+times too large s does shrink, but the first Gaussian pass has already committed the displaced frames as jumps and the
+trajectory stays where it was.  math.inf for a nu makes that side Gaussian; with both infinite the iteration is
+refine_smooth_param_em's.
+
+What it is not: neither nu is fitted; one s per keypoint - no shared s over blocks of keypoints, no grouped weights, no
+h_fn models in the fit; one side cannot be frozen; the planes do not combine with a caller's own frame-interval scale,
+the sampler, increments or innovations.
 """
 from __future__ import annotations
 
+import math
 from typing import Literal
 
 import numpy as np
@@ -37,7 +50,7 @@ import numpy as np
 from . import hip_ops
 from ._problem import check_iteration_counts, linear_problem, singlecam_problem, to_caller
 
-__all__ = ['smooth_heavy_tailed', 'smooth_singlecam_heavy_tailed']
+__all__ = ['smooth_heavy_tailed', 'smooth_singlecam_heavy_tailed', 'fit_heavy_tailed', 'fit_singlecam_heavy_tailed']
 
 
 def smooth_heavy_tailed(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_finals, *, nu_obs: float = 4.0, nu_proc: float = 4.0,
@@ -96,3 +109,57 @@ def smooth_singlecam_heavy_tailed(marker_array, keypoint_names: list, s_finals, 
                 Vs=np.ascontiguousarray(np.swapaxes(Vs, 0, 1)),
                 weights=np.ascontiguousarray(np.swapaxes(weights, 0, 1)),
                 scales=np.ascontiguousarray(np.swapaxes(scales, 0, 1)))
+
+
+def _check_fit(nu_obs, nu_proc, n_iters, log_s_bounds):
+    nus = []
+    for nu in (nu_obs, nu_proc):
+        nu = float(nu)
+        if not nu > 0:                                      # NaN included; math.inf is a Gaussian side
+            raise ValueError('nu must be positive (math.inf: that side is Gaussian)')
+        nus.append(nu)
+    if int(n_iters) != n_iters or n_iters < 1:
+        raise ValueError('n_iters must be an integer >= 1')
+    lo, hi = (float(v) for v in log_s_bounds)
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):            # the C entry's rule; lo == hi pins s
+        raise ValueError('log_s_bounds must be (lo, hi), finite, with lo <= hi')
+    return nus[0], nus[1], int(n_iters), (lo, hi)
+
+
+def fit_heavy_tailed(ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_init, *, nu_obs: float = 4.0, nu_proc: float = 4.0,
+                     n_iters: int = 40, log_s_bounds=(-8.0, 8.0), vs_diag: bool = False, return_device: bool = False,
+                     h_fn=None):
+    """smooth_heavy_tailed that also fits the smoothing parameters: n_iters smoothing passes, every one but the last
+    followed by the updates of both planes and then by the M-step for s (module docstring).  s_init: scalar or (K,),
+    the start - the first pass smooths under it.  Either nu may be math.inf: that side is Gaussian and its plane comes
+    back as ones (general models need a finite nu_obs).  log s is kept inside log_s_bounds (refine_smooth_param_em's
+    default).  Needs at least two frames.
+
+    Returns (ms, Vs, weights, scales, s_fit (K,) float64, change (3,K)): as smooth_heavy_tailed, with s_fit the
+    parameters ms, Vs were smoothed under and change[2] the |delta log s| of the last update."""
+    L = linear_problem('fit_heavy_tailed', ys, m0s, S0s, As, Cs, Qs, ensemble_vars, s_init, h_fn)
+    nu_obs, nu_proc, n_iters, bounds = _check_fit(nu_obs, nu_proc, n_iters, log_s_bounds)
+    if L.T < 2:
+        raise ValueError('fitting s needs at least two frames')
+    P, s_dev = L.upload()
+    ms, Vs, weights, scales, s_fit, change = hip_ops.smooth_heavy_fit(
+        P.y, P.var, *P.params, s_dev, nu_obs=nu_obs, nu_proc=nu_proc, n_iters=n_iters, log_s_bounds=bounds,
+        flags=P.flags, vs_diag=vs_diag)
+    out = to_caller(return_device, (ms, Vs, weights, scales), (change,))
+    return out[:4] + (s_fit if return_device else s_fit.cpu().numpy(), out[4])
+
+
+def fit_singlecam_heavy_tailed(marker_array, keypoint_names: list, s_init, *, nu_obs: float = 4.0,
+                               nu_proc: float = 4.0, n_iters: int = 40, log_s_bounds=(-8.0, 8.0),
+                               avg_mode: Literal['mean', 'median'] = 'median',
+                               var_mode: Literal['var', 'confidence_weighted_var'] = 'confidence_weighted_var') -> dict:
+    """smooth_singlecam_heavy_tailed with the smoothing parameters fitted from the start s_init (fit_heavy_tailed).
+    Returns its dictionary plus s_fit (K,) float64."""
+    _check_fit(nu_obs, nu_proc, n_iters, log_s_bounds)
+    model, _, mu = singlecam_problem('fit_singlecam_heavy_tailed', marker_array, keypoint_names, avg_mode, var_mode)
+    ms, Vs, weights, scales, s_fit, _ = fit_heavy_tailed(*model, s_init, nu_obs=nu_obs, nu_proc=nu_proc, n_iters=n_iters,
+                                                         log_s_bounds=log_s_bounds, vs_diag=True)
+    return dict(ms=np.ascontiguousarray(np.swapaxes(ms, 0, 1)) + mu.astype(np.float32)[None],
+                Vs=np.ascontiguousarray(np.swapaxes(Vs, 0, 1)),
+                weights=np.ascontiguousarray(np.swapaxes(weights, 0, 1)),
+                scales=np.ascontiguousarray(np.swapaxes(scales, 0, 1)), s_fit=s_fit)

@@ -325,17 +325,8 @@ def smooth_jumps(y, var, m0, S0, A, C, Q, s, nu: float = 4.0, n_iters: int = 12,
                             vs_diag, scales, scales_in, want_change)
 
 
-def smooth_heavy(y, var, m0, S0, A, C, Q, s, nu_obs: float = 4.0, nu_proc: float = 4.0, n_iters: int = 12, flags: int = 0,
-                 vs_diag: bool = False, weights=None, scales=None, planes_in: int = 0, want_change: bool = True):
-    """eks_smooth_heavy: eks_smooth under Student-t noise on observations (`nu_obs`, one weight per scalar observation)
-    and process (`nu_proc`, one scale per frame and keypoint) at once, `n_iters` smoothing passes enqueued back to back
-    (include/eks_hip.h has the model).  `weights` (T, K, O) and `scales` (T, K): float32 device tensors that receive
-    the planes; planes_in bit 0 / bit 1: the first pass starts from the contents of weights / scales.  Returns
-    (ms, Vs, weights, scales, change): change is (2, K) float32, row 0 the largest weight change and row 1 the largest
-    change of u = 1 / scale in the last update (None without want_change)."""
-    lib = _lib.load()
-    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
-    dev = bufs[0].device
+def _heavy_planes(weights, scales, planes_in, T, K, O, dev):
+    """The weight and scale planes of smooth_heavy and smooth_heavy_fit, checked or allocated -> (planes_in, [w, s])."""
     planes_in = int(planes_in)
     if planes_in & ~3:
         raise ValueError('planes_in is a mask of bit 0 (weights) and bit 1 (scales)')
@@ -348,6 +339,21 @@ def smooth_heavy(y, var, m0, S0, A, C, Q, s, nu_obs: float = 4.0, nu_proc: float
         elif not plane.is_contiguous():
             raise ValueError(f'{name} must be contiguous: it is written in place')
         planes.append(_chk(plane, torch.float32, name, shape))
+    return planes_in, planes
+
+
+def smooth_heavy(y, var, m0, S0, A, C, Q, s, nu_obs: float = 4.0, nu_proc: float = 4.0, n_iters: int = 12, flags: int = 0,
+                 vs_diag: bool = False, weights=None, scales=None, planes_in: int = 0, want_change: bool = True):
+    """eks_smooth_heavy: eks_smooth under Student-t noise on observations (`nu_obs`, one weight per scalar observation)
+    and process (`nu_proc`, one scale per frame and keypoint) at once, `n_iters` smoothing passes enqueued back to back
+    (include/eks_hip.h has the model).  `weights` (T, K, O) and `scales` (T, K): float32 device tensors that receive
+    the planes; planes_in bit 0 / bit 1: the first pass starts from the contents of weights / scales.  Returns
+    (ms, Vs, weights, scales, change): change is (2, K) float32, row 0 the largest weight change and row 1 the largest
+    change of u = 1 / scale in the last update (None without want_change)."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
+    dev = bufs[0].device
+    planes_in, planes = _heavy_planes(weights, scales, planes_in, T, K, O, dev)
     dims = _dims(K, T, D, O, _vs_flags(flags, vs_diag))
     ms, Vs = _ms_Vs(T, K, D, vs_diag, dev)
     change = torch.empty((2, K), dtype=torch.float32, device=dev) if want_change else None
@@ -357,6 +363,31 @@ def smooth_heavy(y, var, m0, S0, A, C, Q, s, nu_obs: float = 4.0, nu_proc: float
                               ws.numel(), _stream())
     _lib.check(rc, 'eks_smooth_heavy')
     return ms, Vs, planes[0], planes[1], change
+
+
+def smooth_heavy_fit(y, var, m0, S0, A, C, Q, s, nu_obs: float = 4.0, nu_proc: float = 4.0, n_iters: int = 40,
+                     log_s_bounds=(-8.0, 8.0), flags: int = 0, vs_diag: bool = False, weights=None, scales=None,
+                     planes_in: int = 0, want_change: bool = True):
+    """eks_smooth_heavy_fit: eks_smooth_heavy with the M-step for s behind every middle pass (include/eks_hip.h has the
+    model).  `s` (K,) float64 is the start and is not written; either nu may be math.inf (a Gaussian side: its plane
+    comes back as ones and planes_in may not name it).  Returns (ms, Vs, weights, scales, s_fit, change): s_fit (K,)
+    float64 is the s under which ms, Vs were smoothed; change is (3, K) float32, rows 0 and 1 as smooth_heavy's, row 2
+    |delta log s| of the last update (None without want_change)."""
+    lib = _lib.load()
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
+    dev = bufs[0].device
+    planes_in, planes = _heavy_planes(weights, scales, planes_in, T, K, O, dev)
+    dims = _dims(K, T, D, O, _vs_flags(flags, vs_diag))
+    ms, Vs = _ms_Vs(T, K, D, vs_diag, dev)
+    s_fit = torch.empty((K,), dtype=torch.float64, device=dev)
+    change = torch.empty((3, K), dtype=torch.float32, device=dev) if want_change else None
+    ws = _workspace(lib.eks_smooth_heavy_fit_workspace_bytes(ctypes.byref(dims)), dev)
+    rc = lib.eks_smooth_heavy_fit(ctypes.byref(dims), *[_ptr(b) for b in bufs], float(nu_obs), float(nu_proc),
+                                  int(n_iters), float(log_s_bounds[0]), float(log_s_bounds[1]), _ptr(planes[0]),
+                                  _ptr(planes[1]), planes_in, _ptr(change), _ptr(s_fit), _ptr(ms), _ptr(Vs), _ptr(ws),
+                                  ws.numel(), _stream())
+    _lib.check(rc, 'eks_smooth_heavy_fit')
+    return ms, Vs, planes[0], planes[1], s_fit, change
 
 
 def smooth_increments(y, var, m0, S0, A, C, Q, s, flags: int = 0, vs_diag: bool = False,

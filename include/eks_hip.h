@@ -248,6 +248,53 @@ int eks_smooth_heavy(const eks_dims_t* dims, const float* y, const float* var, c
                      int32_t n_iters, float* weights, float* scales, int32_t planes_in, float* change, float* ms,
                      float* Vs, void* workspace, size_t workspace_bytes, eks_stream_t stream);
 
+/* ---- eks_smooth_heavy that also fits the smoothing parameter s, by EM inside the mean-field iteration.  The Gaussian
+ * likelihood explains displaced observations as process noise, so an s found on the Gaussian model is too large in
+ * exactly the sessions the Student-t smoothers exist for.  No reference counterpart.  A middle pass smooths under
+ * (lam, w = 1 / u, s) and makes eks_smooth_heavy's updates of lam and u - same formulas, clamps and launches - and
+ * then, with q(x) and the new q(u) held, maximises the bound over s:
+ *     S_k = sum_{t=1}^{T-1} u_new[t,k] delta[t,k],   s_new = s S_k / n,   n = D (T - 1),
+ * on log s clipped to [log_s_lo, log_s_hi]; delta[t,k] = E[eps_t' (s Q)^-1 eps_t | y] is what the pass stored for the
+ * update of u.  Coordinate ascent: the bound cannot drop.  Everything not named here is eks_smooth_heavy's.
+ *   nu_obs, nu_proc  each > 0; +inf makes that side Gaussian: its plane stays at ones and its update is skipped.  With
+ *               both +inf the iteration is eks_em_scale_run's (tr(Q^-1 Sw) / n) with one keypoint per block.
+ *   s           [K], the start; never written.
+ *   s_out       [K], required; s_out == s is allowed.  The start is copied to it first, every pass reads it, and on
+ *               return it holds the s under which ms and Vs were smoothed.
+ *   log_s_lo, log_s_hi   finite, lo <= hi.  The first pass smooths under s as given; every update is clipped.
+ *   planes_in   as eks_smooth_heavy's; a bit set for a Gaussian side is EKS_ERR_SHAPE.  A Gaussian side's plane, if
+ *               passed, comes back as ones.
+ *   change      float32 [3][K], may be NULL: rows 0 and 1 as eks_smooth_heavy's (0 for a Gaussian side), row 2
+ *               |delta log s| of the call's last update.  The call zeroes all three rows first.
+ *   n_iters     n_iters = 1 is eks_smooth_heavy with n_iters = 1, bit for bit, and s_out = s.  With both nu finite and
+ *               n_iters = 2 the two planes are eks_smooth_heavy's 2-pass planes bit for bit: pass 1 and its updates
+ *               precede the first step.
+ *   continuing  n1 passes continued through both planes and s_out by n2 passes are one call of n1 + n2 - 1 passes,
+ *               bit for bit.
+ *   the sum     float64 in a fixed order that depends on the frame alone - 16 rows, 64 such runs, then the slabs of
+ *               1 024 rows in order; no floating-point atomics - so two calls give the same bits and a call on a subset
+ *               of the keypoints gives that subset's bits (eks_em_stats' contract).  One launch of its own behind the
+ *               combine launch (the block that finishes a keypoint tile last - an integer ticket - adds the slabs and
+ *               makes the step); workspace: eks_smooth_heavy's plus [ceil((T - 1) / 1024)][K] doubles and the tickets.
+ *   s q = 0     such a chain keeps eks_smooth_jumps' convention (its contribution is w), so it counts 1 per frame
+ *               towards S_k.
+ *   NaN         a keypoint whose S_k is not finite (NaN-poisoned input) keeps its s, with 0 in row 2 of change; every
+ *               other keypoint is untouched bit for bit.  An s[k] that is not finite and positive is never stepped.
+ *   general models  nu_obs = +inf is EKS_ERR_UNSUPPORTED (eks_smooth_jumps' general path has no loop to step in); the
+ *               size query takes no nu and cannot say so.
+ *   limits      EM only: from an s 10 .. 100 times too large s does shrink, but the first Gaussian pass has already
+ *               committed the displaced frames as jumps and the trajectory stays where it was.
+ * Refusals: T < 2; a nu that is NaN or not positive; log_s_lo > log_s_hi or a non-finite bound; an input plane on a
+ * Gaussian side (all EKS_ERR_SHAPE); otherwise eks_smooth_heavy's, in the same order, s_out among the outputs.  All
+ * are returned before anything is enqueued and leave every output untouched.  The size query returns 0 for refused
+ * shapes. ------------------ */
+size_t eks_smooth_heavy_fit_workspace_bytes(const eks_dims_t* dims);
+int eks_smooth_heavy_fit(const eks_dims_t* dims, const float* y, const float* var, const double* m0, const double* S0,
+                         const double* A, const double* C, const double* Q, const double* s, double nu_obs,
+                         double nu_proc, int32_t n_iters, double log_s_lo, double log_s_hi, float* weights,
+                         float* scales, int32_t planes_in, float* change, double* s_out, float* ms, float* Vs,
+                         void* workspace, size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- joint posterior trajectories: n_draws draws of x_1..x_T from the smoothing distribution p(x | y) of the model
  * eks_smooth smooths (same dims, flags, y, var and parameters; EKS_FLAG_VS_DIAG is ignored).  No reference counterpart:
  * the reference returns the per-frame marginals ms, Vs only (eks/core.py:296-297), which say nothing about how the
