@@ -21,6 +21,8 @@ def __getattr__(name):          # lazy: pandas/sklearn/torch are only imported w
         'DifferentiableEmission': 'emission',
         'sample_kalman_posterior': 'posterior', 'sample_singlecam': 'posterior',
         'smooth_increments': 'posterior', 'velocity_singlecam': 'posterior',
+        'sample_singlecam_irregular': 'posterior', 'sample_singlecam_heavy_tailed': 'posterior',
+        'sample_multicam_robust': 'posterior',
         'process_noise_statistics': 'em', 'refine_smooth_param_em': 'em', 'fit_process_noise_em': 'em',
         'filter_innovations': 'diagnostics', 'log_likelihood': 'diagnostics', 'innovation_summary': 'diagnostics',
         'innovations_singlecam': 'diagnostics',

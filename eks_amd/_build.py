@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libeks_hip.so')
-SOURCES = ['eks_api.hip', 'eks_diag.hip', 'eks_diag_nll.hip', 'eks_lag_adam.hip', 'eks_chain.hip', 'eks_sample.hip', 'eks_sample_dense.hip', 'eks_increments.hip', 'eks_em.hip', 'eks_innov.hip', 'eks_smooth_tv.hip', 'eks_smooth_student.hip', 'eks_smooth_heavy_fit.hip', 'eks_dense.hip', 'eks_dense_wave.hip', 'eks_dense_wide.hip', 'eks_loss.hip',
+SOURCES = ['eks_api.hip', 'eks_diag.hip', 'eks_diag_nll.hip', 'eks_lag_adam.hip', 'eks_chain.hip', 'eks_sample.hip', 'eks_sample_tv.hip', 'eks_sample_dense.hip', 'eks_increments.hip', 'eks_em.hip', 'eks_innov.hip', 'eks_smooth_tv.hip', 'eks_smooth_student.hip', 'eks_smooth_heavy_fit.hip', 'eks_dense.hip', 'eks_dense_wave.hip', 'eks_dense_wide.hip', 'eks_loss.hip',
            'eks_loss_ar1.hip', 'eks_misc.hip', 'eks_multicam.hip', 'eks_profile.hip', 'eks_host.hip']
 ARCH = 'gfx950'
 
@@ -52,7 +52,7 @@ def _stamp(obj: str) -> str:
 PER_FILE_FLAGS = {'eks_diag_nll.hip': ['-fno-slp-vectorize'], 'eks_lag_adam.hip': ['-fno-slp-vectorize'], 'eks_diag.hip': ['-fno-slp-vectorize'],
                   'eks_chain.hip': ['-fno-slp-vectorize'], 'eks_sample.hip': ['-fno-slp-vectorize'], 'eks_increments.hip': ['-fno-slp-vectorize'], 'eks_em.hip': ['-fno-slp-vectorize'],
                   'eks_innov.hip': ['-fno-slp-vectorize'], 'eks_smooth_tv.hip': ['-fno-slp-vectorize'],
-                  'eks_smooth_student.hip': ['-fno-slp-vectorize']}
+                  'eks_smooth_student.hip': ['-fno-slp-vectorize'], 'eks_sample_tv.hip': ['-fno-slp-vectorize']}
 
 
 def build(force: bool = False, verbose: bool = False, prove: bool = True) -> str:

@@ -66,6 +66,9 @@ SIGNATURES = {
     'eks_sample_workspace_bytes': (c_size_t, [POINTER(EksDims), c_int32]),
     'eks_sample': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 8 + [c_int32, ctypes.c_uint64, c_int32, c_int32]
                    + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    'eks_sample_tv_workspace_bytes': (c_size_t, [POINTER(EksDims), c_int32]),
+    'eks_sample_tv': (ctypes.c_int, [POINTER(EksDims)] + [c_void_p] * 3 + [c_int32] + [c_void_p] * 7
+                      + [c_int32, ctypes.c_uint64, c_int32, c_int32] + [c_void_p] * 4 + [c_size_t, c_void_p]),
     'eks_sample_noise': (ctypes.c_int, [POINTER(EksDims), c_int32, ctypes.c_uint64, c_int32, c_int32, c_void_p, c_void_p]),
     'eks_const_r_workspace_bytes': (c_size_t, [POINTER(EksDims)]),
     'eks_const_r': (ctypes.c_int, [POINTER(EksDims), c_void_p, c_double, c_void_p, c_void_p,

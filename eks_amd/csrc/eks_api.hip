@@ -466,6 +466,44 @@ int eks_sample(const eks_dims_t* d, const float* y, const float* var, const doub
       });
 }
 
+// 0 for every shape eks_sample_tv refuses
+size_t eks_sample_tv_workspace_bytes(const eks_dims_t* d, int32_t n_draws) {
+  return model_bytes(
+      d, n_draws < 1 ? EKS_ERR_SHAPE : smooth_tv_check(d),
+      [&](int T, int N) { return diag_sample_tv_check(T, N, n_draws) == EKS_OK ? diag_sample_workspace_bytes(T, N, n_draws) : 0; },
+      [&](int T, int K, int D, int O) { return dense_sample_tv_workspace_bytes(T, K, D, O, n_draws); });
+}
+
+// Order: eks_sample's refusals in eks_sample's order (dims, n_draws / first_*, the model's pointers, draws, the
+// workspace, and per path its size and launch-index limits), then eks_smooth_tv's shapes.  Only then is anything enqueued.
+int eks_sample_tv(const eks_dims_t* d, const float* y, const float* var, const float* qscale,
+                  int32_t qscale_per_keypoint, const float* weights, const double* m0, const double* S0,
+                  const double* A, const double* C, const double* Q, const double* s, int32_t n_draws, uint64_t seed,
+                  int32_t first_keypoint, int32_t first_draw, const float* noise, float* ms, float* draws,
+                  void* workspace, size_t workspace_bytes, eks_stream_t stream) {
+  const int rc = check_dims(d);
+  if (rc != EKS_OK) return rc;
+  if (n_draws < 1 || first_keypoint < 0 || first_draw < 0) return EKS_ERR_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return model_call(
+      d, {y, var, m0, S0, A, C, Q, s}, !draws ? EKS_ERR_NULL : workspace_status(workspace, workspace_bytes),
+      [&](const DiagModel& M) {
+        const int T = d->n_frames, N = d->n_keypoints * d->state_dim;
+        if (workspace_bytes < diag_sample_workspace_bytes(T, N, n_draws)) return (int)EKS_ERR_WORKSPACE;
+        const int r1 = diag_sample_tv_check(T, N, n_draws);
+        if (r1 != EKS_OK) return r1;
+        const int r2 = diag_smooth_tv_check(*d);
+        if (r2 != EKS_OK) return r2;
+        return diag_sample_tv(*d, y, var, qscale, qscale_per_keypoint, weights, M, n_draws, seed, first_keypoint,
+                              first_draw, noise, ms, draws, workspace, workspace_bytes, st);
+      },
+      [&](const DenseModel& M) {
+        // (dense_sample_tv: eks_sample's limits, which contain eks_smooth_tv's on general models, then the size)
+        return dense_sample_tv(*d, y, var, qscale, qscale_per_keypoint, weights, M, n_draws, seed, first_keypoint,
+                               first_draw, noise, ms, draws, workspace, workspace_bytes, st);
+      });
+}
+
 int eks_sample_noise(const eks_dims_t* d, int32_t n_draws, uint64_t seed, int32_t first_keypoint, int32_t first_draw,
                      float* noise, eks_stream_t stream) {
   const int rc = check_dims(d);

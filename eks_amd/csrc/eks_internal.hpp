@@ -117,6 +117,19 @@ int dense_sample(const eks_dims_t& d, const float* y, const float* var, const De
                  size_t ws_bytes, hipStream_t st);
 int dense_sample_noise(int T, int K, int W, int n_draws, uint64_t seed, int first_keypoint, int first_draw, float* noise,
                        hipStream_t st);
+// the same under a per-frame process-noise scale and observation weights (eks_sample_tv.hip: scalar chains, on
+// diag_sample's workspace; eks_sample_dense.hip: general models).  qscale and weights may be null (every value 1).
+// diag_sample_tv_check: eks_sample's launch-index limits; dense_sample_tv_workspace_bytes: 0 for a refused shape
+int diag_sample_tv_check(int T, int N, int n_draws);
+int diag_sample_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
+                   const float* weights, const DiagModel& M, int n_draws, uint64_t seed, int first_keypoint,
+                   int first_draw, const float* noise, float* ms, float* draws, void* ws, size_t ws_bytes,
+                   hipStream_t st);
+size_t dense_sample_tv_workspace_bytes(int T, int K, int D, int O, int n_draws);
+int dense_sample_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
+                    const float* weights, const DenseModel& M, int n_draws, uint64_t seed, int first_keypoint,
+                    int first_draw, const float* noise, float* ms, float* draws, void* ws, size_t ws_bytes,
+                    hipStream_t st);
 
 // general small-matrix path (eks_dense.hip)
 struct DenseModel {

@@ -17,6 +17,7 @@
 
 #include "eks_internal.hpp"
 #include "eks_sample_lane.hpp"
+#include "eks_smooth_robust_lane.hpp"
 
 namespace eks {
 
@@ -29,7 +30,9 @@ struct DenseSampleWs {
   size_t smooth_ws_bytes;
 };
 
-static size_t dense_sample_carve(int T, int K, int D, int O, int n_draws, char* base, DenseSampleWs* out) {
+// wP != nullptr: dense_sample_tv's layout - a [T][Kp] float scale plane, and dense_smooth_tv's scratch behind it
+static size_t dense_sample_carve(int T, int K, int D, int O, int n_draws, char* base, DenseSampleWs* out,
+                                 float** wP = nullptr) {
   const size_t Kp = ((size_t)n_draws + 1) * K;
   size_t at = 0;
   auto take = [&](size_t bytes) {
@@ -48,7 +51,8 @@ static size_t dense_sample_carve(int T, int K, int D, int O, int n_draws, char* 
   w.C = (double*)take(Kp * O * D * 8);
   w.Q = (double*)take(Kp * D * D * 8);
   w.s = (double*)take(Kp * 8);
-  w.smooth_ws_bytes = dense_smooth_workspace_bytes(T, (int)Kp, D, O);
+  if (wP) *wP = (float*)take((size_t)T * Kp * 4);
+  w.smooth_ws_bytes = wP ? dense_smooth_tv_workspace_bytes(T, (int)Kp, D, O) : dense_smooth_workspace_bytes(T, (int)Kp, D, O);
   w.smooth_ws = take(w.smooth_ws_bytes);
   if (out) *out = w;
   return at;
@@ -211,6 +215,155 @@ int dense_sample(const eks_dims_t& d, const float* y, const float* var, const De
   dp.flags = (d.flags & ~(uint32_t)(EKS_FLAG_DIAG_MODEL | EKS_FLAG_UNIT_AC)) | EKS_FLAG_VS_DIAG;
   const DenseModel MP{P.m0, P.S0, P.A, P.C, P.Q, P.s};
   const int rc = dense_smooth(dp, P.yP, P.varP, MP, P.msP, P.VsP, P.smooth_ws, P.smooth_ws_bytes, st);
+  if (rc != EKS_OK) return rc;
+  {
+    ProfScope ps("dense_sample_combine", st);
+    const size_t n = (size_t)T * K * D;
+    hipLaunchKernelGGL(dense_sample_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, T, K, D, n_draws,
+                       P.msP, ms, draws);
+  }
+  return hip_status(hipGetLastError());
+}
+
+// ---- eks_sample_tv: the same three steps under a per-frame process-noise scale w and observation weights lam --------
+//   1. dense_sample_tv_simulate : as above with the state noise of the step INTO frame t scaled by sqrt(w_t) and the
+//                                 observation noise drawn at r_eff = robust_var(var, lam); r_eff goes into varP
+//   2. dense_sample_tv_scale    : the stacked problem's [T][Kp] scale plane (every set reads its keypoint's w; 1
+//                                 without qscale)
+//   3. dense_smooth_tv on the stacked problem, then dense_sample_combine as above
+// w at frame t is qscale[t] (shared) or qscale[t][k]; row 0 is never read.
+__device__ __forceinline__ float dense_tv_scale(const float* qscale, int per_keypoint, int K, int t, int k) {
+  return qscale ? qscale[per_keypoint ? (size_t)t * K + k : (size_t)t] : 1.0f;
+}
+
+// thread = (frame t, stacked chain): row 0 is written as 1 (dense_smooth_tv never reads it; a NaN there stays out)
+__global__ __launch_bounds__(256) void dense_sample_tv_scale_kernel(int T, int K, int n_draws, const float* qscale,
+                                                                    int per_keypoint, float* wP) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t Kp = ((size_t)n_draws + 1) * K;
+  if (idx >= (size_t)T * Kp) return;
+  const int t = (int)(idx / Kp), k = (int)((idx % Kp) % K);
+  wP[idx] = t == 0 ? 1.0f : dense_tv_scale(qscale, per_keypoint, K, t, k);
+}
+
+// thread = (keypoint k, set), as dense_sample_simulate_kernel
+template <int D>
+__global__ __launch_bounds__(64) void dense_sample_tv_simulate_kernel(int T, int K, int O, int n_draws, const float* y,
+                                                                      const float* var, const float* qscale,
+                                                                      int per_keypoint, const float* weights,
+                                                                      DenseModel M, DenseSampleWs P, const float* noise,
+                                                                      float* draws, uint32_t k0, uint32_t k1,
+                                                                      uint32_t kp_base, uint32_t d_base) {
+  const int idx = blockIdx.x * 64 + threadIdx.x;
+  const size_t Kp = ((size_t)n_draws + 1) * K;
+  if ((size_t)idx >= Kp) return;
+  const int k = idx % K, set = idx / K;
+  for (int i = 0; i < D; ++i) P.m0[(size_t)idx * D + i] = set == 0 ? M.m0[(size_t)k * D + i] : 0.0;
+  for (int i = 0; i < D * D; ++i) {
+    P.S0[(size_t)idx * D * D + i] = M.S0[(size_t)k * D * D + i];
+    P.A[(size_t)idx * D * D + i] = M.A[(size_t)k * D * D + i];
+    P.Q[(size_t)idx * D * D + i] = M.Q[(size_t)k * D * D + i];
+  }
+  for (int i = 0; i < O * D; ++i) P.C[(size_t)idx * O * D + i] = M.C[(size_t)k * O * D + i];
+  P.s[idx] = M.s[k];
+  auto r_eff = [&](size_t src) { return weights ? robust_var(var[src], weights[src]) : clip_var(var[src]); };
+  if (set == 0) {
+    for (int t = 0; t < T; ++t)
+      for (int o = 0; o < O; ++o) {
+        const size_t src = ((size_t)t * K + k) * O + o, dst = ((size_t)t * Kp + idx) * O + o;
+        P.yP[dst] = y[src];
+        P.varP[dst] = r_eff(src);
+      }
+    return;
+  }
+  const int d = set - 1;
+  double S0m[D][D], Qm[D][D], Am[D][D], L0[D][D], Lq[D][D];
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      S0m[i][j] = M.S0[(size_t)k * D * D + i * D + j];
+      Qm[i][j] = M.s[k] * M.Q[(size_t)k * D * D + i * D + j];
+      Am[i][j] = M.A[(size_t)k * D * D + i * D + j];
+    }
+  chol_psd<D>(S0m, L0);
+  chol_psd<D>(Qm, Lq);
+  const double* Cm = M.C + (size_t)k * O * D;
+  const int W = D + O;
+  double x[D];
+  for (int i = 0; i < D; ++i) x[i] = 0.0;
+  float z[kDenseNoiseMax];
+  for (int t = 0; t < T; ++t) {
+    if (noise) {
+      const float* zr = noise + (((size_t)d * T + t) * K + k) * W;
+      for (int w = 0; w < W; ++w) z[w] = zr[w];
+    } else {
+      dense_normals(k0, k1, t, kp_base + k, d_base + d, W, z);
+    }
+    // chol(s w_t Q) = sqrt(w_t) chol(s Q)
+    const double sw = t == 0 ? 1.0 : sqrt((double)dense_tv_scale(qscale, per_keypoint, K, t, k));
+    double xn[D];
+    for (int i = 0; i < D; ++i) {
+      double v = 0.0;
+      if (t > 0)
+        for (int j = 0; j < D; ++j) v += Am[i][j] * x[j];
+      for (int j = 0; j <= i; ++j) v += (t == 0 ? L0[i][j] : sw * Lq[i][j]) * (double)z[j];
+      xn[i] = v;
+    }
+    for (int i = 0; i < D; ++i) {
+      x[i] = xn[i];
+      draws[(((size_t)d * T + t) * K + k) * D + i] = (float)x[i];
+    }
+    for (int o = 0; o < O; ++o) {
+      double v = 0.0;
+      for (int j = 0; j < D; ++j) v += Cm[o * D + j] * x[j];
+      const float r = r_eff(((size_t)t * K + k) * O + o);
+      v += sqrt((double)r) * (double)z[D + o];
+      const size_t dst = ((size_t)t * Kp + idx) * O + o;
+      P.yP[dst] = (float)v;
+      P.varP[dst] = r;
+    }
+  }
+}
+
+// 0 where dense_sample_tv refuses the shape with EKS_ERR_SHAPE (the caller has checked D <= 6, O <= 64)
+size_t dense_sample_tv_workspace_bytes(int T, int K, int D, int O, int n_draws) {
+  const size_t Kp = ((size_t)n_draws + 1) * K;
+  if (Kp * D > (1u << 24) || (size_t)T * Kp >= ((size_t)1 << 38)) return 0;
+  if (!dense_smooth_tv_workspace_bytes(T, (int)Kp, D, O)) return 0;
+  float* wP;
+  return dense_sample_carve(T, K, D, O, n_draws, nullptr, nullptr, &wP);
+}
+
+int dense_sample_tv(const eks_dims_t& d, const float* y, const float* var, const float* qscale, int per_keypoint,
+                    const float* weights, const DenseModel& M, int n_draws, uint64_t seed, int first_keypoint,
+                    int first_draw, const float* noise, float* ms, float* draws, void* ws, size_t ws_bytes,
+                    hipStream_t st) {
+  const int T = d.n_frames, K = d.n_keypoints, D = d.state_dim, O = d.obs_dim;
+  if (D < 1 || D > 6 || O < 1 || O > 64) return EKS_ERR_UNSUPPORTED;
+  const size_t Kp = ((size_t)n_draws + 1) * K;
+  const size_t need = dense_sample_tv_workspace_bytes(T, K, D, O, n_draws);
+  if (!need) return EKS_ERR_SHAPE;
+  if (ws_bytes < need) return EKS_ERR_WORKSPACE;
+  DenseSampleWs P;
+  float* wP;
+  dense_sample_carve(T, K, D, O, n_draws, static_cast<char*>(ws), &P, &wP);
+  const int pk = per_keypoint ? 1 : 0;
+  {
+    ProfScope ps("dense_sample_tv_simulate", st);
+    EKS_DISPATCH_D(D, hipLaunchKernelGGL((dense_sample_tv_simulate_kernel<DD>), dim3((unsigned)((Kp + 63) / 64)), dim3(64),
+                                         0, st, T, K, O, n_draws, y, var, qscale, pk, weights, M, P, noise, draws,
+                                         (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)first_keypoint,
+                                         (uint32_t)first_draw));
+  }
+  {
+    ProfScope ps("dense_sample_tv_scale", st);
+    hipLaunchKernelGGL(dense_sample_tv_scale_kernel, dim3((unsigned)(((size_t)T * Kp + 255) / 256)), dim3(256), 0, st, T, K,
+                       n_draws, qscale, pk, wP);
+  }
+  eks_dims_t dp = d;
+  dp.n_keypoints = (int)Kp;
+  dp.flags = (d.flags & ~(uint32_t)(EKS_FLAG_DIAG_MODEL | EKS_FLAG_UNIT_AC)) | EKS_FLAG_VS_DIAG;
+  const DenseModel MP{P.m0, P.S0, P.A, P.C, P.Q, P.s};
+  const int rc = dense_smooth_tv(dp, P.yP, P.varP, wP, 1, MP, P.msP, P.VsP, P.smooth_ws, P.smooth_ws_bytes, st);
   if (rc != EKS_OK) return rc;
   {
     ProfScope ps("dense_sample_combine", st);

@@ -38,7 +38,7 @@ refine_smooth_param_em's.
 
 What it is not: neither nu is fitted; one s per keypoint - no shared s over blocks of keypoints, no grouped weights, no
 h_fn models in the fit; one side cannot be frozen; the planes do not combine with a caller's own frame-interval scale,
-the sampler, increments or innovations.
+increments or innovations (trajectory draws under them: eks_amd.posterior.sample_singlecam_heavy_tailed).
 """
 from __future__ import annotations
 

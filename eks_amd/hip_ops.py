@@ -518,6 +518,44 @@ def sample(y, var, m0, S0, A, C, Q, s, n_draws: int, seed: int = 0, flags: int =
     return draws, ms
 
 
+def sample_tv_workspace_bytes(K: int, T: int, D: int, O: int, flags: int, n_draws: int) -> int:
+    """eks_sample_tv_workspace_bytes: 0 for a shape eks_sample_tv refuses."""
+    return int(_lib.load().eks_sample_tv_workspace_bytes(ctypes.byref(_dims(K, T, D, O, _vs_flags(flags, True))),
+                                                         int(n_draws)))
+
+
+def sample_tv(y, var, m0, S0, A, C, Q, s, n_draws: int, qscale=None, weights=None, seed: int = 0, flags: int = 0,
+              first_keypoint: int = 0, first_draw: int = 0, noise=None, want_mean: bool = False, out=None):
+    """eks_sample_tv: sample() under x_t = A x_{t-1} + N(0, s w_t Q), y_t = C x_t + N(0, robust_var(var, lam)).
+    qscale: float32 device tensor (T,) or (T, K) as smooth_tv's (row 0 never read), or None for w = 1; weights: float32
+    (T, K, O), every value finite and > 0, or None for lam = 1.  Everything else, the generator included, is sample()'s.
+    (The Vs-shape flag is set: no Vs is returned, and eks_smooth_tv's D <= 8 limit on full Vs rows does not apply.)"""
+    lib = _lib.load()
+    n_draws = int(n_draws)
+    if n_draws < 1:
+        raise ValueError('n_draws must be at least 1')
+    (T, K, O, D), bufs = _model_args(y, var, m0, S0, A, C, Q, s)
+    dims = _dims(K, T, D, O, _vs_flags(flags, True))
+    if qscale is not None:
+        if qscale.dim() not in (1, 2):
+            raise ValueError(f'qscale must have shape {(T,)} or {(T, K)}, got {tuple(qscale.shape)}')
+        qscale = _chk(qscale, torch.float32, 'qscale', (T,) if qscale.dim() == 1 else (T, K))
+    if weights is not None:
+        weights = _chk(weights, torch.float32, 'weights', (T, K, O))
+    if noise is not None:
+        noise = _chk(noise, torch.float32, 'noise', (n_draws, T, K, lib.eks_sample_noise_width(ctypes.byref(dims))))
+    draws = torch.empty((n_draws, T, K, D), dtype=torch.float32, device=y.device) if out is None \
+        else _chk(out, torch.float32, 'out', (n_draws, T, K, D))
+    ms = torch.empty((T, K, D), dtype=torch.float32, device=y.device) if want_mean else None
+    ws = _workspace(lib.eks_sample_tv_workspace_bytes(ctypes.byref(dims), n_draws), y.device)
+    rc = lib.eks_sample_tv(ctypes.byref(dims), _ptr(bufs[0]), _ptr(bufs[1]), _ptr(qscale),
+                           int(qscale is not None and qscale.dim() == 2), _ptr(weights), *[_ptr(b) for b in bufs[2:]],
+                           n_draws, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_keypoint), int(first_draw), _ptr(noise),
+                           _ptr(ms), _ptr(draws), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, 'eks_sample_tv')
+    return draws, ms
+
+
 def sample_noise(T: int, K: int, D: int, O: int, n_draws: int, seed: int = 0, flags: int = 0, first_keypoint: int = 0,
                  first_draw: int = 0):
     """eks_sample_noise: the normals eks_sample(seed) generates, (n_draws, T, K, W) float32."""

@@ -331,6 +331,33 @@ int eks_sample(const eks_dims_t* dims, const float* y, const float* var, const d
 int eks_sample_noise(const eks_dims_t* dims, int32_t n_draws, uint64_t seed, int32_t first_keypoint,
                      int32_t first_draw, float* noise, eks_stream_t stream);
 
+/* ---- eks_sample under a per-frame process-noise scale and observation weights: draws from the smoothing distribution of
+ *   x_t = A x_{t-1} + N(0, s w_t Q),     y_t = C x_t + N(0, r_eff,t),     r_eff,t = clip(clip(var_t) / lam_t)
+ * - eks_smooth_tv's model at lam = 1, and the Gaussian factor of the mean-field posteriors of eks_smooth_robust,
+ * eks_smooth_robust_group, eks_smooth_jumps, eks_smooth_heavy and eks_smooth_heavy_fit at the planes they return (nu
+ * does not enter).  No reference counterpart.
+ *   qscale   float32 [T] (qscale_per_keypoint == 0) or [T][K], eks_smooth_tv's convention: the scale of the step INTO
+ *            frame t; row 0 is never read (a NaN there changes nothing).  NULL: every scale is 1.  Precondition as
+ *            there: 0 <= w <= 1e6, finite.
+ *   weights  float32 [T][K][O] as eks_smooth_robust's; every value finite and > 0 (the caller's precondition; a
+ *            grouped plane is expanded to one value per coordinate by the caller).  NULL: every weight is 1.
+ * dims, flags, y, var, the parameters, n_draws, seed, first_keypoint, first_draw, noise, ms, draws, the generator, its
+ * counter layout and the noise width are exactly eks_sample's; eks_sample_noise serves both entries.
+ *   scalar chains   eks_sample's seven launches (eks_amd/csrc/eks_sample_tv.hip): frame t's filter step, gain G_t and
+ *            innovation sd_t all read w[t + 1]; the session's last frame has G = 0, sd = sqrt(Pf).  The variances are
+ *            reweighted in registers.  Workspace: eks_sample's.
+ *   general models  Durbin & Koopman as eks_sample, the state noise of the step into frame t scaled by sqrt(w_t), the
+ *            observation noise drawn at r_eff, and the stacked call eks_smooth_tv's (eks_amd/csrc/eks_sample_dense.hip).
+ * Refusals: eks_sample's in eks_sample's order, then eks_smooth_tv's for the shape; all are returned before anything
+ * is enqueued, and eks_sample_tv_workspace_bytes returns 0 for every refused shape.  Every workspace plane is written
+ * by the call before the call reads it. ------------ */
+size_t eks_sample_tv_workspace_bytes(const eks_dims_t* dims, int32_t n_draws);
+int eks_sample_tv(const eks_dims_t* dims, const float* y, const float* var, const float* qscale,
+                  int32_t qscale_per_keypoint, const float* weights, const double* m0, const double* S0,
+                  const double* A, const double* C, const double* Q, const double* s, int32_t n_draws, uint64_t seed,
+                  int32_t first_keypoint, int32_t first_draw, const float* noise, float* ms, float* draws,
+                  void* workspace, size_t workspace_bytes, eks_stream_t stream);
+
 /* ---- eks_smooth plus the posterior of frame-to-frame increments.  No reference counterpart: the variance of
  * x_{t+1} - x_t (velocity, speed, movement onsets) is not a function of the marginals ms, Vs; it needs
  * Cov(x_t, x_{t+1} | y), which the RTS step holds in closed form.  dims, flags, inputs and the ms / Vs layouts are
